@@ -13,11 +13,21 @@ each rank owns; only the voxel count and checksum travel to rank 0).
 That is BASELINE.json's metric ("voxels/sec sliding-window 3D U-Net inference, 2048x2048x1024 vol @
 1/2/4/8 GPU"); the volume and its window list are the same at every N, so scaling is "strong".
 
-Rank 0 prints ONE JSON line.  `value` comes from EXACTLY --steps passes with no per-kernel instrumentation; the same
-passes are then repeated with every launch bracketed by HIP events on the engine's stream (dlv_prof_*) for `kernels`
-and `roofline`, once more with the background skip disabled for `value_dense`, and `cpu_baseline` times the CPU oracle
-(oracle/, a port of the reference's algorithm) on BASELINE.md section 3's bounded samples on the host cores of this
-box and checks that the HIP path gives the same result on that sample.
+Rank 0 prints ONE JSON line.  `value` comes from EXACTLY --steps passes with no per-kernel instrumentation.  A plain run
+does only that: set-up, --warmup passes, the --steps timed passes, the outputs of the last one (--dump-outputs DIR), the
+line.  With --full the same passes are then repeated with every launch bracketed by HIP events on the engine's stream
+(dlv_prof_*) for `kernels` and `roofline`, once more with the background skip disabled for `value_dense`, once in the other
+16-bit format, the stages either side of the pass are timed (`extras`), the file -> file steps (`step_walls`), and
+`cpu_baseline` times the CPU oracle (oracle/, a port of the reference's algorithm) on BASELINE.md section 3's bounded
+samples on the host cores of this box and checks that the HIP path gives the same result on that sample.  The --no-*
+switches leave single legs of --full out.
+
+--dump-outputs DIR writes what the last timed pass computed, in float32 (40 MB at the 1024 x 2048 x 2048 volume):
+  mask_row_counts.npy   (Z, Y): foreground voxels of the uint8 mask per (z, y) row - every voxel of the mask counts
+  mask_sample.npy       the mask (0 / 1) at a fixed sample of DUMP_SAMPLES voxel positions (all voxels of a smaller stack)
+  logit_sum_sample.npy  the blended logit sums (the fp32 accumulator the mask is thresholded from) at the same positions
+The positions are np.unique(default_rng(DUMP_SEED).integers(0, Z*Y*X, DUMP_SAMPLES)) as flat (z, y, x) indices of the
+stack; the volume is synthetic and seeded, so the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -52,6 +62,54 @@ TRAINED_LIKE_FIXTURE = os.environ.get("DLV_TRAINED_LIKE_FIXTURE") or os.path.joi
 PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
 FLOP_PER_PATCH_VOXEL = 285104.0
+DUMP_SAMPLES = 1 << 22  # voxel positions of the --dump-outputs sample (before duplicates are dropped)
+DUMP_SEED = 20240917
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, slab, own_lo, acc, acc_z0, stack, dist, rank, host_reduce):
+    """--dump-outputs: the mask of the last timed pass (row counts + the seeded sample) and the blended logit sums at the same
+    positions, as float32 .npy files in out_dir (written by rank 0).  slab holds planes [own_lo, own_lo + n) of the stack's mask
+    (the planes this rank owns), acc planes [acc_z0, ...) of the padded volume's sums.  N > 1: every rank fills the rows and
+    positions of its own planes and the zeros elsewhere are summed away (all_reduce: every plane has one owner).  Returns the
+    `outputs` block of the bench line (None on ranks other than 0)."""
+    import torch
+
+    Z, Y, X = (int(v) for v in stack)
+    n_vox = Z * Y * X
+    dev = acc.device
+    idx = (np.arange(n_vox, dtype=np.int64) if n_vox <= DUMP_SAMPLES
+           else np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_vox, size=DUMP_SAMPLES, dtype=np.int64)))
+    idx_d = torch.from_numpy(idx).to(dev)
+    z, y, x = idx_d // (Y * X), (idx_d // X) % Y, idx_d % X
+    n_own = int(slab.shape[0])
+    rows = torch.zeros((Z, Y), dtype=torch.float32, device=dev)
+    mask_s = torch.zeros(idx.size, dtype=torch.float32, device=dev)
+    logit_s = torch.zeros(idx.size, dtype=torch.float32, device=dev)
+    if n_own:
+        rows[own_lo:own_lo + n_own] = slab[:, :Y, :X].sum(dim=2, dtype=torch.int32).to(torch.float32)
+        mine = (z >= own_lo) & (z < own_lo + n_own)
+        zm, ym, xm = z[mine], y[mine], x[mine]
+        mask_s[mine] = slab[zm - own_lo, ym, xm].to(torch.float32)
+        logit_s[mine] = acc[zm - acc_z0, ym, xm]
+    out = {"mask_row_counts": rows, "mask_sample": mask_s, "logit_sum_sample": logit_s}
+    if dist is not None:
+        for k, t in out.items():
+            if host_reduce:  # (gloo reduces host tensors)
+                t = t.cpu()
+            dist.all_reduce(t)
+            out[k] = t
+    if rank != 0:
+        return None
+    arrs = {k: t.cpu().numpy().astype(np.float32, copy=False) for k, t in out.items()}
+    nbytes = sum(a.nbytes for a in arrs.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {nbytes} bytes exceed the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": {k + ".npy": list(a.shape) for k, a in arrs.items()}, "bytes": nbytes, "dtype": "float32",
+            "sample_seed": DUMP_SEED, "sample_positions": int(idx.size)}
 
 
 def _cpu_info():
@@ -459,12 +517,18 @@ def main():
                     help="trained (default): the trained-like checkpoint (tests/golden/trained_like_weights.npz: top levels trained on the "
                          "reference's patches + synth volumes, deep levels seeded random; bimodal logits, a mask of small blobs); "
                          "random: seeded random weights (margin-free logits, one giant component)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed passes, also run every other leg: the per-kernel HIP-event view and roofline, the dense pass, "
+                         "the other 16-bit format, the stages either side of the pass, the file -> file step walls and the CPU baseline "
+                         "with its agreement check (each can be left out with its --no-* switch); off: only what `value` needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed pass computed to DIR/*.npy (float32, at most 64 MB: see the module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-crop", type=int, default=256, help="edge of the centre crop the CPU baseline runs (256: 27 windows of 128^3)")
     ap.add_argument("--no-dense", action="store_true", help="skip the extra pass with the background skip disabled (`value_dense`)")
     ap.add_argument("--no-prof", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the stages either side of the pass (finalize, CCL-26 + statistics, "
-                    "resamplers, one Gaussian-blend pass: BASELINE configs 4/5), which run by default at N=1")
+                    "resamplers, one Gaussian-blend pass: BASELINE configs 4/5), which --full runs at N=1")
     ap.add_argument("--no-isolated", action="store_true", help="skip the extra single-lane step that times the kernels alone")
     ap.add_argument("--diag", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B runs: a kernel-selection switch of include/delivr_hip_diag.h (dlv_diag_set) for the benchmark's engine, e.g. "
@@ -473,6 +537,8 @@ def main():
     ap.add_argument("--no-step-walls", action="store_true", help="skip the file -> file wall-clock of run_inference and count_blobs "
                     "on this volume (N = 1; ~30 GiB of files on /dev/shm for c3)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.step_walls_child:
         step_walls_child(args.step_walls_child)
@@ -647,9 +713,13 @@ def main():
     # the timed region: EXACTLY `steps` passes, no per-kernel event bracketing inside it
     elapsed, slab = timed_steps(args.steps)
     stats_timed = dict(stats_last)
+    outputs = None
+    if args.dump_outputs:  # (before any leg of --full overwrites acc / the mask)
+        outputs = dump_outputs(args.dump_outputs, slab, plan.z_owned[rank][0] if dist_mode else 0, acc, slo, (Z, Y, X),
+                               dist if dist_mode else None, rank, dist_mode and dist.get_backend() == "gloo")
     # the same passes again with the HIP-event bracketing of every launch switched on (dlv_prof_*): the per-kernel view
     prof, elapsed_prof = {}, None
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         eng.prof_reset()
         eng.prof_enable(True)
         elapsed_prof, _ = timed_steps(args.steps)
@@ -657,7 +727,7 @@ def main():
         eng.prof_enable(False)
     # every window through the network (background skip disabled): the number the MFMA ceiling is quoted against
     elapsed_dense, stats_dense = None, {}
-    if not args.no_dense and not args.dense:
+    if args.full and not args.no_dense and not args.dense:
         cur["params"] = pass_params(args.precision, -1)  # skip_threshold -1: no window's maximum is <= -1
         elapsed_dense, _ = timed_steps(1)
         stats_dense = dict(stats_last)
@@ -665,7 +735,7 @@ def main():
     # N > 1: where a rank's step goes - its windows, the seam exchange, the finalize of the planes it owns - from one extra step with
     # a synchronisation after every phase (the first 8-GPU record can be held against DESIGN section 6's model line by line)
     per_rank_phases = None
-    if dist_mode:
+    if dist_mode and args.full:
         fence()
         step(phases=True)
         fence()
@@ -676,12 +746,12 @@ def main():
         dist.all_gather_object(per_rank_phases, mine)
     # the other 16-bit format, one pass (BASELINE's configs name bf16; fp16 is the default for its closer masks)
     elapsed_alt, alt_prec = None, {"fp16": "bf16", "bf16": "fp16"}.get(args.precision)
-    if alt_prec and not args.no_dense and not args.dense:
+    if args.full and alt_prec and not args.no_dense and not args.dense:
         cur["params"] = pass_params(alt_prec)
         step()  # warm-up of the other format's kernels
         elapsed_alt, _ = timed_steps(1)
         cur["params"] = params
-    if not args.no_dense and not args.dense:
+    if args.full and not args.no_dense and not args.dense:
         slab = step()  # leave acc / slab holding the benchmark's own pass (the extras and the CPU leg read them)
         fence()
     stats_last.clear()
@@ -827,7 +897,7 @@ def main():
     # every entry: ms per call on this volume, the ALGORITHMIC HBM bytes of the stage (inputs read once + outputs written
     # once, stated per voxel), and hbm_frac = bytes / time / 8 TB/s
     extras = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         def timed(fn, reps=2):
             fn()
             eng.sync()
@@ -915,14 +985,14 @@ def main():
             del vol_d, acc_d, mask_d
 
     walls = None
-    if not args.no_step_walls and world == 1 and not dist_mode:
+    if args.full and not args.no_step_walls and world == 1 and not dist_mode:
         try:
             walls = step_walls(eng, vol, stack, shape, roi, tta, args.precision, sd, mask_voxels, weights_name)
         except Exception as exc:  # reported, never fatal for the metric
             walls = {"skipped": f"failed: {exc!r}"}
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N=1 only (bench contract)
+    if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N=1 only (bench contract)
         try:
             threads = os.cpu_count() or 1
             cpu = cpu_baseline(eng, sd, vol, stack, roi, n_active * n_passes, vox, threads, args.cpu_crop, args.precision, weights_name, acc, nb)
@@ -979,10 +1049,12 @@ def main():
         "roofline": roofline_isolated if roofline_isolated is not None else roofline,
         "roofline_timed_region": roofline if roofline_isolated is not None else None,
         "cpu_baseline": cpu,
-        "kernels": kernels,
+        "kernels": kernels if args.full else None,
         "extras": extras,
         # the step boundary: wall clock file -> file of the two steps, with the H2D / D2H transfers timed separately
         "step_walls": walls,
+        "full": bool(args.full),  # (off: every leg after the timed passes was left out and reports null)
+        "outputs": outputs,       # --dump-outputs: the files the last timed pass's results were written to
     }
     print(json.dumps(out))
     if dist_mode:

@@ -211,6 +211,13 @@ def load() -> C.CDLL:
         raise ImportError(
             f"{LIB_PATH} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C delivr_cfos_amd/csrc` (hipcc, --offload-arch=gfx950). There is no CPU fallback.")
+    # ONE HIP runtime per process: torch for ROCm carries its own libamdhip64 (SONAME libamdhip64.so.7, which it loads by the
+    # unversioned name).  Loaded first, it is the libamdhip64.so.7 this library asks for.  Loaded after this library, it would
+    # map a second runtime beside ROCm's, and every context of this library then fails (dlv_ctx_create: DLV_EHIP).
+    try:
+        import torch  # noqa: F401
+    except ImportError:  # (a process without torch: the C ABI alone, ROCm's runtime)
+        pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing

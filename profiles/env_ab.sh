@@ -8,9 +8,9 @@ for round in 1 2; do
 for setting in "$@"; do
   out=gpurun_out/$TAG/$(echo $setting | tr '= ' '__')_r$round.json
   if [ "$setting" = "-" ]; then
-    timeout 900 python3 bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-prof --no-isolated > $out 2>/dev/null
+    timeout 900 python3 bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-prof --no-isolated > $out 2>/dev/null
   else
-    env $setting timeout 900 python3 bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-prof --no-isolated > $out 2>/dev/null
+    env $setting timeout 900 python3 bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-prof --no-isolated > $out 2>/dev/null
   fi
   python3 - "$out" "$setting" <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ mkdir -p gpurun_out/$TAG
 for round in 1 2; do
 for L in $LIBS; do
   out=gpurun_out/$TAG/${L%.so}_r$round.json
-  DLV_LIB=$L timeout 900 python3 bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-dense > $out 2> gpurun_out/$TAG/${L%.so}_r$round.err
+  DLV_LIB=$L timeout 900 python3 bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-dense > $out 2> ${out%.json}.err
   python3 - "$out" "$L" <<'PY'
 import json, sys
 try:

@@ -8,10 +8,10 @@ TAG=${1:-r04m}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp
-python3 $R/bench.py --steps 3 --warmup 1 > $OUT/c3_bench.json 2> $OUT/c3_bench.err
-DLV_LANES=1 python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $OUT/c3_bench_1lane.json 2> $OUT/c3_bench_1lane.err
-python3 $R/bench.py --precision bf16 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $OUT/c3_bench_bf16.json 2> $OUT/c3_bench_bf16.err
-python3 $R/bench.py --workload c2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/c2_bench.json 2> $OUT/c2_bench.err
+python3 $R/bench.py --full --steps 3 --warmup 1 > $OUT/c3_bench.json 2> $OUT/c3_bench.err
+DLV_LANES=1 python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $OUT/c3_bench_1lane.json 2> $OUT/c3_bench_1lane.err
+python3 $R/bench.py --full --precision bf16 --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $OUT/c3_bench_bf16.json 2> $OUT/c3_bench_bf16.err
+python3 $R/bench.py --full --workload c2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/c2_bench.json 2> $OUT/c2_bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3_3lane -- python3 $R/bench.py --workload c3 --steps 1 --warmup 1 --no-cpu-baseline --no-dense --no-prof --no-extras > $OUT/c3_3lane_prof.log 2>&1
 DLV_LANES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3_1lane -- python3 $R/bench.py --workload c3 --steps 1 --warmup 1 --no-cpu-baseline --no-dense --no-prof --no-extras > $OUT/c3_1lane_prof.log 2>&1
 DLV_LANES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2_1lane -- python3 $R/bench.py --workload c2 --steps 2 --warmup 1 --no-cpu-baseline --no-dense --no-prof --no-extras > $OUT/c2_1lane_prof.log 2>&1

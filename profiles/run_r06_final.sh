@@ -15,10 +15,10 @@ cd $R
 bash profiles/run_pmc_traffic.sh ${TAG}_traffic c2 fp16 > $OUT/traffic.log 2>&1
 cp $R/gpurun_out/${TAG}_traffic/traffic_r06_c2.json $R/profiles/traffic_r06_c2.json
 cd /tmp
-python3 $R/bench.py --steps 3 --warmup 1 > $OUT/c3_bench.json 2> $OUT/c3_bench.err
-python3 $R/bench.py --workload default --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-step-walls > $OUT/default_bench.json 2> $OUT/default_bench.err
-python3 $R/bench.py --workload legacy --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-step-walls > $OUT/legacy_bench.json 2> $OUT/legacy_bench.err
-python3 $R/bench.py --workload c2 --steps 3 --warmup 1 --no-cpu-baseline --no-step-walls > $OUT/c2_bench.json 2> $OUT/c2_bench.err
+python3 $R/bench.py --full --steps 3 --warmup 1 > $OUT/c3_bench.json 2> $OUT/c3_bench.err
+python3 $R/bench.py --full --workload default --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-step-walls > $OUT/default_bench.json 2> $OUT/default_bench.err
+python3 $R/bench.py --full --workload legacy --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-step-walls > $OUT/legacy_bench.json 2> $OUT/legacy_bench.err
+python3 $R/bench.py --full --workload c2 --steps 3 --warmup 1 --no-cpu-baseline --no-step-walls > $OUT/c2_bench.json 2> $OUT/c2_bench.err
 LIGHT="--steps 1 --warmup 1 --no-cpu-baseline --no-dense --no-prof --no-extras --no-step-walls"
 DLV_LANES=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3_1lane -- python3 $R/bench.py --workload c3 $LIGHT > $OUT/c3_1lane_prof.log 2>&1
 rm -f $OUT/*/*/*kernel_trace.csv

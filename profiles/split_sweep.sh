@@ -8,7 +8,7 @@ mkdir -p gpurun_out/$TAG
 for cfg in $CONFIGS; do
   IFS=: read split lanes swb <<< "$cfg"
   out=gpurun_out/$TAG/split${split}_lanes${lanes}_b${swb:-0}.json
-  DLV_CU_SPLIT=$split DLV_LANES=$lanes timeout 600 python3 bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras \
+  DLV_CU_SPLIT=$split DLV_LANES=$lanes timeout 600 python3 bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-extras \
       --no-prof --no-isolated --sw-batch ${swb:-0} > $out 2> gpurun_out/$TAG/split${split}_lanes${lanes}_b${swb:-0}.err
   python3 - "$out" "$cfg" <<'PY'
 import json, sys

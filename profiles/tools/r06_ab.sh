@@ -8,7 +8,8 @@ out=gpurun_out/${tag}_ab.txt
 run() {  # workload steps diag...
   wl=$1; steps=$2; shift 2
   name=$(echo "$wl $*" | tr ' =' '__' | tr -d '-')
-  python bench.py --workload $wl --steps $steps --warmup 1 --no-cpu-baseline --no-dense --no-extras --no-step-walls --no-isolated "$@" > gpurun_out/${tag}_${name}.json 2> gpurun_out/${tag}_${name}.err
+  dir=$(dirname "$out")
+  python bench.py --full --workload $wl --steps $steps --warmup 1 --no-cpu-baseline --no-dense --no-extras --no-step-walls --no-isolated "$@" > "$dir/${tag}_${name}.json" 2> "$dir/${tag}_${name}.err"
   python - "$wl" "$*" gpurun_out/${tag}_${name}.json >> $out <<'P'
 import json, sys
 try:

@@ -36,6 +36,26 @@ def test_library_exports_every_declared_symbol():
     assert lib.dlv_abi_version() == 2
 
 
+def test_library_loaded_before_torch_shares_torch_hip_runtime():
+    """_lib.load() in a process that has not imported torch yet (build() then smoke(), or this file's tests ahead of the GPU
+    ones): the library must bind to the libamdhip64 torch brings, not map ROCm's beside it - with two HIP runtimes in one
+    process every context of the library fails to create."""
+    import ast
+    import subprocess
+    import sys
+
+    _ensure_built()
+    code = ("import sys; sys.path.insert(0, sys.argv[1])\n"
+            "from delivr_cfos_amd import _lib\n"
+            "_lib.load()\n"
+            "import torch\n"
+            "print(sorted({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))\n")
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    runtimes = ast.literal_eval(r.stdout.strip().splitlines()[-1])
+    assert len(runtimes) == 1, runtimes
+
+
 def test_host_tiler_matches_reference_golden(golden_dir):
     _lib = _ensure_built()
     lib = _lib.load()

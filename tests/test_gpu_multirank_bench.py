@@ -14,7 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "1", "--warmup", "0", "--workload", "tiny", "--no-cpu-baseline", "--no-extras", "--no-isolated"]
+COMMON = ["--steps", "1", "--warmup", "0", "--workload", "tiny", "--full", "--no-cpu-baseline", "--no-extras", "--no-isolated"]
 
 
 def _free_port():
@@ -67,7 +67,7 @@ def test_padded_volume_with_tta_schedule_sharded_three_ways_matches_the_single_r
     config.json:24-28,63) at plumbing size: a stack of 100 x 180 x 150 zero-padded to 192^3, on one rank and on three."""
     env = dict(os.environ)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    args = ["--steps", "1", "--warmup", "0", "--workload", "tiny_default", "--no-cpu-baseline", "--no-extras", "--no-isolated", "--no-step-walls"]
+    args = ["--steps", "1", "--warmup", "0", "--workload", "tiny_default", "--full", "--no-cpu-baseline", "--no-extras", "--no-isolated", "--no-step-walls"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args], capture_output=True, text=True, timeout=900,
                          env=env, cwd=ROOT)
     assert one.returncode == 0, one.stdout + one.stderr

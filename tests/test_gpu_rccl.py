@@ -82,7 +82,7 @@ def _json_line(out):
 
 
 def test_bench_at_world_one_on_the_nccl_backend_matches_the_plain_line():
-    common = ["--steps", "1", "--warmup", "0", "--workload", "tiny", "--no-cpu-baseline", "--no-extras", "--no-isolated"]
+    common = ["--steps", "1", "--warmup", "0", "--workload", "tiny", "--full", "--no-cpu-baseline", "--no-extras", "--no-isolated"]
     env = dict(os.environ)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *common], capture_output=True, text=True,

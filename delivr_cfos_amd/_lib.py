@@ -153,6 +153,8 @@ SIGNATURES = {
     "dlv_bcast_weights": (C.c_int, [_P, C.c_int]),
     "dlv_sw_infer_sharded": (C.c_int, [_P, C.POINTER(SwParams), C.POINTER(ShardPlanC), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                        C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(SwStats)]),
+    "dlv_sw_infer_sharded_wsum": (C.c_int, [_P, C.POINTER(SwParams), C.POINTER(ShardPlanC), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(SwStats)]),
     "dlv_finalize_slab_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                         C.c_int, _P, _P]),
     "dlv_finalize_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,

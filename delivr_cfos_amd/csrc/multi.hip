@@ -7,6 +7,7 @@
 //   dlv_sw_infer_sharded  every rank runs its window range on ITS slab of the volume / accumulator (one host thread per
 //                         rank), then ONE point-to-point exchange per seam (ncclSend/ncclRecv, grouped): the planes a
 //                         rank computed but another rank owns are added by the owner in source-rank order
+//                         (dlv_sw_infer_sharded_wsum: the same with a weight-sum slab per rank for the Gaussian blend)
 // RCCL is loaded with dlopen at dlv_comm_init_all (a single-GPU host never needs librccl.so); ranks that share a device
 // (tests on a one-GPU box) exchange with hipMemcpyAsync instead.  No all-reduce exists on this path: xGMI is
 // point-to-point, every seam crosses exactly one link.
@@ -490,13 +491,15 @@ int dlv_comm_range_recover(dlv_comm* c, int* n_changed) {
     DLV_ABI_GUARD_END(c)
 }
 
-int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_plan* plan, const int* slab_z0, const int* slab_nz,
-                         const uint16_t* const* vol_slab_dev, float* const* acc_slab_dev, uint8_t* const* cnt_slab_dev,
-                         dlv_sw_stats* stats) {
+int dlv_sw_infer_sharded_wsum(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_plan* plan, const int* slab_z0,
+                              const int* slab_nz, const uint16_t* const* vol_slab_dev, float* const* acc_slab_dev,
+                              uint8_t* const* cnt_slab_dev, float* const* wsum_slab_dev, dlv_sw_stats* stats) {
     if (!c || !p || !plan || !slab_z0 || !slab_nz || !vol_slab_dev || !acc_slab_dev) return DLV_EINVAL;
     DLV_ABI_GUARD_BEGIN
     if (plan->world != c->n) return comm_fail(c, DLV_EINVAL, "plan for %d ranks, communicator has %d", plan->world, c->n);
     const int n = c->n;
+    // the weight sums exist (and travel with the sums) only in Gaussian mode; constant mode ignores them like p->wsum_dev
+    float* const* wsum = p->blend_mode == DLV_BLEND_GAUSSIAN ? wsum_slab_dev : nullptr;
     const size_t plane = (size_t)p->Yp * p->Xp;
     for (int r = 0; r < n; ++r) {
         const bool live = plan->win_end[r] > plan->win_begin[r];
@@ -527,6 +530,7 @@ int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_pl
                 q.win_end = plan->win_end[r];
                 q.z0 = slab_z0[r];
                 q.nz = slab_nz[r];
+                q.wsum_dev = wsum ? wsum[r] : nullptr;  // every rank its own weight-sum slab
                 rcs[r] = dlv_sw_infer_dev(c->ctx[r], &q, vol_slab_dev[r], acc_slab_dev[r], cnt_slab_dev ? cnt_slab_dev[r] : nullptr,
                                           stats ? &stats[r] : nullptr);
             });
@@ -541,7 +545,7 @@ int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_pl
     };
     std::vector<Seam> seams;
     std::vector<size_t> need(n, 0);
-    const size_t bpv = 4 + (cnt_slab_dev ? 1 : 0);  // staged bytes per voxel: fp32 sum (+ uint8 count)
+    const size_t bpv = 4 + (wsum ? 4 : 0) + (cnt_slab_dev ? 1 : 0);  // staged bytes per voxel: fp32 sum (+ fp32 weight sum) (+ uint8 count)
     for (int dst = 0; dst < n; ++dst)
         for (int src = 0; src < n; ++src) {  // increasing source rank = the order of the additions
             if (src == dst || plan->win_end[src] <= plan->win_begin[src]) continue;
@@ -565,17 +569,22 @@ int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_pl
         const float* sa = acc_slab_dev[s.src] + (size_t)(s.lo - slab_z0[s.src]) * plane;
         float* da = reinterpret_cast<float*>(stg[s.dst] + s.off);
         const uint8_t* sc = cnt_slab_dev ? cnt_slab_dev[s.src] + (size_t)(s.lo - slab_z0[s.src]) * plane : nullptr;
-        uint8_t* dc = reinterpret_cast<uint8_t*>(stg[s.dst] + s.off + nvox * 4);
+        const float* sw = wsum ? wsum[s.src] + (size_t)(s.lo - slab_z0[s.src]) * plane : nullptr;
+        float* dw = reinterpret_cast<float*>(stg[s.dst] + s.off + nvox * 4);
+        uint8_t* dc = reinterpret_cast<uint8_t*>(stg[s.dst] + s.off + nvox * (wsum ? 8 : 4));
         if (rccl) {
             DLV_CHIP(c, hipSetDevice(c->devs[s.src]));
             DLV_NCCL(c, c->Send(sa, nvox, ncclFloat32, s.dst, c->comm[s.src], c->ctx[s.src]->main_stream));
+            if (sw) DLV_NCCL(c, c->Send(sw, nvox, ncclFloat32, s.dst, c->comm[s.src], c->ctx[s.src]->main_stream));
             if (sc) DLV_NCCL(c, c->Send(sc, nvox, ncclUint8, s.dst, c->comm[s.src], c->ctx[s.src]->main_stream));
             DLV_CHIP(c, hipSetDevice(c->devs[s.dst]));
             DLV_NCCL(c, c->Recv(da, nvox, ncclFloat32, s.src, c->comm[s.dst], c->ctx[s.dst]->main_stream));
+            if (sw) DLV_NCCL(c, c->Recv(dw, nvox, ncclFloat32, s.src, c->comm[s.dst], c->ctx[s.dst]->main_stream));
             if (sc) DLV_NCCL(c, c->Recv(dc, nvox, ncclUint8, s.src, c->comm[s.dst], c->ctx[s.dst]->main_stream));
         } else {  // ranks on one device (tests): plain device copies on the owner's stream
             DLV_CHIP(c, hipSetDevice(c->devs[s.dst]));
             DLV_CHIP(c, hipMemcpyAsync(da, sa, nvox * 4, hipMemcpyDeviceToDevice, c->ctx[s.dst]->main_stream));
+            if (sw) DLV_CHIP(c, hipMemcpyAsync(dw, sw, nvox * 4, hipMemcpyDeviceToDevice, c->ctx[s.dst]->main_stream));
             if (sc) DLV_CHIP(c, hipMemcpyAsync(dc, sc, nvox, hipMemcpyDeviceToDevice, c->ctx[s.dst]->main_stream));
         }
     }
@@ -594,10 +603,14 @@ int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_pl
         const int grid = (int)std::min<size_t>((nvox + 255) / 256, 256 * 32);
         hipLaunchKernelGGL(add_f32_kernel, dim3(grid), dim3(256), 0, c->ctx[s.dst]->main_stream,
                            acc_slab_dev[s.dst] + (size_t)(s.lo - slab_z0[s.dst]) * plane, reinterpret_cast<const float*>(stg[s.dst] + s.off), nvox);
+        if (wsum)
+            hipLaunchKernelGGL(add_f32_kernel, dim3(grid), dim3(256), 0, c->ctx[s.dst]->main_stream,
+                               wsum[s.dst] + (size_t)(s.lo - slab_z0[s.dst]) * plane,
+                               reinterpret_cast<const float*>(stg[s.dst] + s.off + nvox * 4), nvox);
         if (cnt_slab_dev)
             hipLaunchKernelGGL(add_u8_kernel, dim3(grid), dim3(256), 0, c->ctx[s.dst]->main_stream,
                                cnt_slab_dev[s.dst] + (size_t)(s.lo - slab_z0[s.dst]) * plane,
-                               reinterpret_cast<const uint8_t*>(stg[s.dst] + s.off + nvox * 4), nvox);
+                               reinterpret_cast<const uint8_t*>(stg[s.dst] + s.off + nvox * (wsum ? 8 : 4)), nvox);
         if (hipGetLastError() != hipSuccess) return comm_fail(c, DLV_EHIP, "launch of the seam add kernel failed");
     }
     for (int r = 0; r < n; ++r) {
@@ -606,6 +619,19 @@ int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_pl
     }
     return DLV_OK;
     DLV_ABI_GUARD_END(c)
+}
+
+int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_plan* plan, const int* slab_z0, const int* slab_nz,
+                         const uint16_t* const* vol_slab_dev, float* const* acc_slab_dev, uint8_t* const* cnt_slab_dev,
+                         dlv_sw_stats* stats) {
+    if (!c || !p) return DLV_EINVAL;
+    // one p->wsum_dev cannot be every rank's weight-sum slab (the ranks would add into the same memory)
+    if (c->n > 1 && p->blend_mode == DLV_BLEND_GAUSSIAN && p->wsum_dev)
+        return comm_fail(c, DLV_EINVAL, "dlv_sw_infer_sharded: Gaussian blend over %d ranks with p->wsum_dev set - pass one weight-sum "
+                         "slab per rank to dlv_sw_infer_sharded_wsum", c->n);
+    float* one[1] = {p->wsum_dev};  // (one rank: its weight sums are p->wsum_dev, as before)
+    return dlv_sw_infer_sharded_wsum(c, p, plan, slab_z0, slab_nz, vol_slab_dev, acc_slab_dev, cnt_slab_dev,
+                                     c->n == 1 && p->wsum_dev ? one : nullptr, stats);
 }
 
 }  // extern "C"

@@ -103,8 +103,9 @@ class HipComm:
 
         return plan_from_params(params, len(self.devices), weights)
 
-    def sw_infer_sharded(self, params, plan, slabs, vols, accs, cnts=None):
-        """slabs[r] = (z0, nz); vols / accs / cnts: per-rank tensors on devices[r] holding those planes."""
+    def sw_infer_sharded(self, params, plan, slabs, vols, accs, cnts=None, wsums=None):
+        """slabs[r] = (z0, nz); vols / accs / cnts: per-rank tensors on devices[r] holding those planes.  wsums: per-rank fp32
+        weight-sum slabs of the Gaussian blend (dlv_sw_infer_sharded_wsum; params.wsum_dev is then ignored)."""
         n = len(self.devices)
         pc = _lib.ShardPlanC()
         pc.world, pc.n_windows = n, plan.n_windows
@@ -123,11 +124,27 @@ class HipComm:
         st = (_lib.SwStats * n)()
         for d in set(self.devices):
             torch.cuda.synchronize(d)
-        self._check(self.lib.dlv_sw_infer_sharded(self.handle, C.byref(params), C.byref(pc), z0, nz, vp, ap, cp, st))
+        if wsums is None:
+            self._check(self.lib.dlv_sw_infer_sharded(self.handle, C.byref(params), C.byref(pc), z0, nz, vp, ap, cp, st))
+        else:
+            wp = (C.c_void_p * n)(*[self.engines[r]._dev(wsums[r], torch.float32, "wsum").value for r in range(n)])
+            self._check(self.lib.dlv_sw_infer_sharded_wsum(self.handle, C.byref(params), C.byref(pc), z0, nz, vp, ap, cp, wp, st))
         return [{"n_windows": s.n_windows, "n_skipped": s.n_skipped, "n_forward_launches": s.n_forward_launches} for s in st]
 
 
 _shared_engines: Dict[int, "HipEngine"] = {}
+_shared_comms: Dict[Tuple[int, ...], HipComm] = {}
+
+
+def shared_comm(devices: Sequence[int]) -> HipComm:
+    """The process-wide communicator of a device tuple (run_inference with settings["mi355x"]["devices"]): initialised once per
+    process like shared_engine's engines, its contexts keep their workspaces and seam staging between brains."""
+    key = tuple(int(d) for d in devices)
+    comm = _shared_comms.get(key)
+    if comm is None or comm.handle is None:
+        comm = HipComm(key)
+        _shared_comms[key] = comm
+    return comm
 
 
 def shared_engine(device: int = 0) -> "HipEngine":

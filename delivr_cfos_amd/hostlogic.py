@@ -24,6 +24,49 @@ def arrayterator_zblock(shape_zyx: Sequence[int], buf_size: int = 1000**3) -> in
     return Z if count >= Z else max(count, 1)
 
 
+MAX_RANKS = 16  # DLV_MAX_RANKS (include/delivr_hip.h): ranks of one communicator
+
+
+def resolve_devices(cuda_devices, setting, device_count: int, group_world: int = 1) -> List[int]:
+    """The devices run_inference shards one volume over, from its ``cuda_devices`` argument ("0,1" in the reference) and
+    settings["mi355x"]["devices"]:
+      None / "first"  the first entry of cuda_devices, 0 when it is empty or not visible (what run_inference always did),
+      "all"           every entry of cuda_devices (the reference's DataParallel spans them all),
+      [i, j, ...]     these devices in this order; repeats are ranks that share a device.
+    `group_world`: world size of the torch.distributed group this process is a rank of (1: none) - such a rank has one device.
+    Raises ValueError for anything else: an unknown string, an empty list, an index that is negative or not visible (only the
+    default keeps its fall-back to 0), more than one device inside a process group, more ranks than a communicator holds."""
+    if setting is None or (isinstance(setting, str) and setting == "first"):
+        first = int(str(cuda_devices).split(",")[0]) if str(cuda_devices).strip() else 0
+        return [first if first < int(device_count) else 0]
+    if isinstance(setting, str):
+        if setting != "all":
+            raise ValueError(f"settings['mi355x']['devices'] = {setting!r}: expected \"first\", \"all\" or a list of device indices")
+        try:
+            devs = [int(t) for t in str(cuda_devices).split(",") if t.strip()]
+        except ValueError:
+            raise ValueError(f"cuda_devices {cuda_devices!r}: expected comma-separated device indices") from None
+        if not devs:
+            raise ValueError("settings['mi355x']['devices'] = \"all\" with an empty cuda_devices")
+    elif isinstance(setting, (list, tuple)):
+        if not setting:
+            raise ValueError("settings['mi355x']['devices']: an empty list names no device")
+        if any(isinstance(d, bool) or not isinstance(d, (int, np.integer)) for d in setting):
+            raise ValueError(f"settings['mi355x']['devices'] = {setting!r}: device indices must be integers")
+        devs = [int(d) for d in setting]
+    else:
+        raise ValueError(f"settings['mi355x']['devices'] = {setting!r}: expected \"first\", \"all\" or a list of device indices")
+    bad = [d for d in devs if d < 0 or d >= int(device_count)]
+    if bad:
+        raise ValueError(f"devices {devs}: {bad} not among the {int(device_count)} visible device(s)")
+    if len(devs) > 1 and int(group_world) > 1:
+        raise ValueError(f"devices {devs}: this process is one rank of a torch.distributed group of {int(group_world)} - "
+                         "each rank runs on one device (its LOCAL_RANK)")
+    if len(devs) > MAX_RANKS:
+        raise ValueError(f"devices {devs}: at most {MAX_RANKS} ranks per process")
+    return devs
+
+
 def pass_schedule(tta: bool) -> List[Tuple[Optional[int], int]]:
     """(flip_dim, repeat) per DISTINCT pass.  The reference runs 1 plain pass, then 4 x {noise,
     noise + flip Z (dim 2), noise + flip Y (dim 3)} (inference/inference.py:261-279); its noise is

@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ..hostio import save_npy
-from ..hostlogic import arrayterator_zblock, padded_shape, pass_schedule
+from ..hostlogic import arrayterator_zblock, padded_shape, pass_schedule, resolve_devices
 from .._lib import DLV_ERANGE, DelivrHipError
 from ..range_guard import next_shifts, run_with_range_recovery
 from ..model import HipBasicUNet
@@ -66,6 +66,162 @@ def create_nifti_seg(threshold, model_output, output_file, network_output_file, 
     return mask
 
 
+def _check_uint8_count(eng, padded, crop_size, overlap, precision, tta):
+    """uint8 like the reference's LOAD_ALL_RAM map (:241): refuse geometries whose multiplicity cannot be held"""
+    from ..hostlogic import max_window_multiplicity
+
+    p_chk = eng.make_sw_params(padded, crop_size, overlap, None, 0, precision)
+    mult = max_window_multiplicity(eng.window_starts(p_chk), [int(p_chk.roi[k]) for k in range(3)]) * (13 if tta else 1)
+    if mult > 255:
+        raise NotImplementedError(f"up to {mult} (window, pass) contributions per voxel do not fit the uint8 count map "
+                                  "(overlap too large for this threshold / SAVE_ACTIVATED_OUTPUT setting)")
+
+
+def _run_multi_device(devices, niftis, output_folder, stack_shape, comment, model_weights, state_dict, tta, threshold, crop_size,
+                      overlap, precision, settings, mark):
+    """run_inference over several devices from one process (the reference's DataParallel over cuda_devices): the C-ABI
+    communicator of the device tuple (engine.shared_comm: rank r on devices[r]; ranks that share a device exchange with device
+    copies, distinct devices with RCCL) runs the plan of parallel.balanced_plans - every rank uploads and accumulates only its
+    Z-slab, the plan is balanced by the windows that run the network -, one dlv_sw_infer_sharded(_wsum) per distinct pass, the
+    seam sums added by their owners in rank order; every rank finalizes the planes it owns and writes them into the files
+    itself.  Sets run_inference.last_shards."""
+    import torch
+
+    from .. import hostio
+    from ..engine import shared_comm
+    from ..parallel import balanced_plans, finalize_owned
+    from ..streaming import forward_workspace_bytes, hbm_budget_bytes, inference_bytes_per_voxel
+
+    world = len(devices)
+    comm = shared_comm(devices)  # (initialised once per process and device tuple: contexts and workspaces stay between brains)
+    engines = comm.engines
+    if state_dict is None:
+        state_dict = torch.load(os.path.abspath(model_weights), map_location="cpu", weights_only=False)
+    engines[0].load_state_dict(state_dict)
+    comm.bcast_weights(0)  # ONE broadcast of the packed blob instead of DataParallel's per-forward replicate
+    mark("model")
+    mi = (settings or {}).get("mi355x", {})
+    gaussian = mi.get("blend", "constant") == "gaussian"
+    save_activated = bool(settings and settings.get("FLAGS", {}).get("SAVE_ACTIVATED_OUTPUT"))
+    need_count = save_activated or float(threshold) != 0.5
+    cm_dtype = torch.float32 if gaussian else torch.uint8
+
+    print(f"{datetime.datetime.now()} : Loading Data (sharded over devices {list(devices)})")
+    stack_shape = tuple(int(v) for v in stack_shape)
+    Z, Y, X = stack_shape[2:]
+    pad = padded_shape(stack_shape[2:], crop_size)
+    dataset_host = np.memmap(niftis[0], dtype=np.uint16, mode="r", shape=(1, 1) + pad, offset=128)
+    os.makedirs(os.path.join(output_folder, comment), exist_ok=True)
+    if need_count and cm_dtype == torch.uint8:
+        _check_uint8_count(engines[0], pad, crop_size, overlap, precision, tta)
+    nb = arrayterator_zblock((Z, Y, X))
+    p_all = engines[0].make_sw_params(pad, crop_size, overlap, None, 0, precision)
+
+    # Does every device hold the slabs of its ranks (volume + sums (+ count map) + finalize maps) and one forward workspace per
+    # rank?  Budgets are taken before the first upload; a rank's workspace already counts as held when its context has served
+    # these windows in this format (then it is not in the device's free memory any more; an explicit hbm_budget_gb is a total)
+    budgets = {d: hbm_budget_bytes(engines[devices.index(d)], settings) for d in sorted(set(devices))}
+    bpv = inference_bytes_per_voxel(need_count, gaussian, save_activated)
+    ws_key = (tuple(crop_size), precision)
+    explicit_budget = bool(mi.get("hbm_budget_gb"))
+
+    def check_memory(plan):
+        need = dict.fromkeys(budgets, 0)
+        for r, d in enumerate(devices):
+            lo, hi = plan.slab(r, Z, 30, nb)
+            held = not explicit_budget and ws_key in engines[r].__dict__.get("_ws_reserved", set())
+            need[d] += (hi - lo) * int(pad[1]) * int(pad[2]) * bpv + (0 if held else forward_workspace_bytes(crop_size, precision))
+        for d, n in need.items():
+            if n > budgets[d]:
+                ranks = [r for r, e in enumerate(devices) if e == d]
+                raise MemoryError(f"device {d}: the slabs of ranks {ranks} ({bpv} B per voxel of {int(pad[1])} x {int(pad[2])} planes) "
+                                  f"and their forward workspaces need {n / 2**30:.2f} GiB, the HBM budget is {budgets[d] / 2**30:.2f} "
+                                  "GiB (settings['mi355x']['hbm_budget_gb']); use more devices or smaller windows - slabs are not "
+                                  "streamed on this path")
+
+    fetchers = [lambda lo, hi, e=e: e.upload_volume(dataset_host[0, 0], lo, hi) for e in engines]
+    shards = balanced_plans(engines, p_all, fetchers, world, list(range(world)), lambda maxima: maxima, Z, 30, nb,
+                            check=check_memory)
+    plan = shards[0][0]
+    slabs = [(lo, hi - lo) for _p, lo, hi, _v in shards]
+    vols = [v for _p, _lo, _hi, v in shards]
+    accs = [torch.zeros((n,) + tuple(pad[1:]), dtype=torch.float32, device=e.device) for (_lo, n), e in zip(slabs, engines)]
+    cnts = ([torch.zeros((n,) + tuple(pad[1:]), dtype=cm_dtype, device=e.device) for (_lo, n), e in zip(slabs, engines)]
+            if need_count else None)
+    mark("upload+alloc")
+
+    print(f"{datetime.datetime.now()} : Starting inference")
+    stats = None
+    for attempt in range(6):
+        try:
+            for flip_dim, repeat in pass_schedule(bool(tta)):
+                p = engines[0].make_sw_params(pad, crop_size, overlap, flip_dim, 0, precision, repeat=repeat,
+                                              blend="gaussian" if gaussian else "constant")
+                stats = comm.sw_infer_sharded(p, plan, slabs, vols, accs, None if gaussian else cnts,
+                                              wsums=cnts if gaussian else None)
+                # the planes a rank computed for another one have been added by their owner: cleared, so that the next pass's
+                # exchange sends only that pass's partial sums
+                for r, (slo, _n) in enumerate(slabs):
+                    for _dst, lo, hi in plan.sends(r):
+                        for t in [accs[r]] + ([cnts[r]] if cnts is not None else []):
+                            t[lo - slo:hi - slo].zero_()
+            break
+        except DelivrHipError as e:
+            if e.code != DLV_ERANGE or precision not in ("fp16", "bf16"):
+                raise
+            print(f"WARNING: {e}")
+        # the range guard on every rank at once: dlv_comm_range_recover gives every rank the same next block shifts (from the
+        # largest layer named and the largest peaks of all ranks), so the slabs keep composing into one mask
+        before = engines[0].conv_shifts()
+        try:
+            changed = comm.range_recover() if attempt < 4 else 0
+        except DelivrHipError as e:
+            if e.code != DLV_ERANGE:
+                raise
+            changed = 0
+        if changed:
+            for blk, k in enumerate(engines[0].conv_shifts()):
+                if k != before[blk]:
+                    print(f"WARNING: conv block {blk}: storing its raw output scaled by 2^-{k} on every rank and repeating the passes "
+                          f"in {precision}")
+        else:
+            print("WARNING: repeating the inference passes with bf16 operands at every level on every rank")
+            precision = "bf16_all"
+        for t in accs + (cnts or []):
+            t.zero_()
+    else:  # (not reachable: the bf16_all attempt either succeeds or raises)
+        raise RuntimeError("range guard: the passes did not come to an end in six attempts")
+    for e in engines:
+        e.__dict__.setdefault("_ws_reserved", set()).add(ws_key)
+    mark("passes")
+
+    # every rank finalizes the planes it owns and writes them into the one file at their offset: no gather to one device
+    print(f"{datetime.datetime.now()} : Creating binarized blob output")
+    testing_session_path = os.path.abspath(output_folder + "/" + comment)
+    binaries_path = testing_session_path + "/binary_segmentations/"
+    os.makedirs(binaries_path, exist_ok=True)
+    output_file = os.path.join(binaries_path, "binaries.npy")
+    off = hostio.create_npy(output_file, np.uint8, (Z, Y, X))
+    if save_activated:
+        os.makedirs(testing_session_path + "/network_outputs/", exist_ok=True)
+        network_output_file = os.path.join(binaries_path, "network_output.npy")
+        poff = hostio.create_npy(network_output_file, np.float32, (Z, Y, X))
+    shards_out = []
+    for r, e in enumerate(engines):
+        slo = slabs[r][0]
+        mask, prob, (lo, hi) = finalize_owned(e, plan, r, accs[r], None if cnts is None else cnts[r], vols[r], (Z, Y, X), threshold,
+                                              30, want_prob=save_activated, z0=slo)
+        e.sync()
+        if mask is not None:
+            hostio.download(e, mask, output_file, offset=off + lo * Y * X, what="d2h_mask", sparse=True)
+            if save_activated:
+                hostio.download(e, prob, network_output_file, offset=poff + lo * Y * X * 4, what="d2h_prob", sparse=True)
+        olo, ohi = plan.z_owned[r]
+        shards_out.append({"device": int(devices[r]), "windows": int(stats[r]["n_windows"]), "skipped": int(stats[r]["n_skipped"]),
+                           "owned": (min(olo, Z), min(ohi, Z)), "slab": (slo, slo + slabs[r][1])})
+    run_inference.last_shards = shards_out
+
+
 def run_inference(
     niftis,
     output_folder,
@@ -94,12 +250,21 @@ def run_inference(
     Pipelining over several brains (python -m delivr_cfos_amd does it; single device, resident volumes): ``prefetch`` = the
     masked_nifti.npy of the NEXT brain - it is read into HBM by a side thread while this brain's passes run, and the next call
     finds it there; ``defer_write`` = return when the mask exists in HBM, binaries.npy streams out in the background
-    (hostio.wait_deferred() before anything reads the file).  Per brain the step then costs its passes."""
+    (hostio.wait_deferred() before anything reads the file).  Per brain the step then costs its passes.
+
+    Several devices from one process: settings["mi355x"]["devices"] = "all" (every entry of ``cuda_devices``, the reference's
+    DataParallel) or a list of device indices (hostlogic.resolve_devices; absent or "first": the first entry of cuda_devices,
+    as always).  When it resolves to more than one device outside a torch.distributed group, the window list is sharded over
+    them through the C-ABI communicator (_run_multi_device): every device holds only its ranks' Z-slabs.  That path does not
+    honour ``prefetch`` and ``defer_write``: its files are complete when the call returns.  run_inference.last_shards then
+    lists one dict per rank: device, windows, skipped (of one pass), owned and slab (plane ranges [lo, hi)); it is None after a
+    call on one device per process."""
     import time
 
     import torch
 
     marks = [("start", time.perf_counter())]  # wall-clock marks of this call -> run_inference.last_timings (bench.py: step2_wall_s)
+    run_inference.last_shards = None  # (set by the multi-device branch only)
 
     def mark(name):
         marks.append((name, time.perf_counter()))
@@ -130,12 +295,22 @@ def run_inference(
     sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank = dist.get_rank() if sharded else 0
     world = dist.get_world_size() if sharded else 1
+    # settings["mi355x"]["devices"]: absent / "first" = the first entry of cuda_devices; "all" / a list = several devices
+    devices = resolve_devices(cuda_devices, (settings or {}).get("mi355x", {}).get("devices"), torch.cuda.device_count(), world)
     if sharded:
         device_index = int(os.environ.get("LOCAL_RANK", rank))
     else:
-        device_index = int(str(cuda_devices).split(",")[0]) if str(cuda_devices).strip() else 0
+        device_index = devices[0]
     if device_index >= torch.cuda.device_count():
         device_index = 0
+    if not sharded and len(devices) > 1:
+        _run_multi_device(devices, niftis, output_folder, stack_shape, comment, model_weights, state_dict, tta, threshold,
+                          crop_size, overlap, precision, settings, mark)
+        mark("finalize+write")
+        run_inference.last_timings = {"total_s": marks[-1][1] - marks[0][1],
+                                      **{f"{b[0]}_s": b[1] - a[1] for a, b in zip(marks, marks[1:])}}
+        print(f"{datetime.datetime.now()} : Blob Detection finished")
+        return os.path.abspath(output_folder + "/" + comment)
 
     # ~~<< M O D E L >>~~  (reference :190-222)
     # the process-wide engine of the device: its context, workspaces and pinned staging survive between brains and steps
@@ -269,14 +444,7 @@ def run_inference(
         prealloc_t = side.get("t", {})
         mark("upload+alloc")
     if need_count and cm_dtype == torch.uint8:
-        # uint8 like the reference's LOAD_ALL_RAM map (:241): refuse geometries whose multiplicity cannot be held
-        from ..hostlogic import max_window_multiplicity
-
-        p_chk = eng.make_sw_params(pad[2:], crop_size, overlap, None, 0, precision)
-        mult = max_window_multiplicity(eng.window_starts(p_chk), [int(p_chk.roi[k]) for k in range(3)]) * (13 if tta else 1)
-        if mult > 255:
-            raise NotImplementedError(f"up to {mult} (window, pass) contributions per voxel do not fit the uint8 count map "
-                                      "(overlap too large for this threshold / SAVE_ACTIVATED_OUTPUT setting)")
+        _check_uint8_count(eng, pad[2:], crop_size, overlap, precision, tta)
     print("output_image shape", tuple(pad[2:]))
 
     testing_session_path = os.path.abspath(output_folder + "/" + comment)

@@ -160,27 +160,50 @@ def balanced_plan(engine, params, fetch_planes, world: int, rank: int, dist, Z: 
       2. one small all_gather of the maxima -> plan balanced by the windows that actually run the network,
       3. every rank completes its final slab (planes it already holds are re-used).
     Returns (plan, slab_lo, slab_hi, vol_slab)."""
-    import torch
+    def all_gather(mine):
+        parts = [None] * world
+        dist.all_gather_object(parts, mine[0])
+        return parts
 
+    return balanced_plans([engine], params, [fetch_planes], world, [rank], all_gather, Z, erode_iters, zblock)[0]
+
+
+def balanced_plans(engines, params, fetchers, world: int, ranks, exchange, Z: int, erode_iters: int = 30, zblock: int = 0,
+                   check=None):
+    """The steps of balanced_plan for the ranks this process drives: `engines[i]` and `fetchers[i]` serve rank `ranks[i]`.
+    `exchange(maxima of these ranks)` -> the window maxima of every rank in rank order: all_gather_object across the processes
+    of a torch.distributed group (balanced_plan), the list itself when one process drives every rank (HipComm).  `check(plan)`
+    (optional) sees the balanced plan before any slab is completed.  Returns [(plan, slab_lo, slab_hi, vol_slab)] per rank."""
     from . import _lib
 
     plan0 = plan_from_params(params, world, None)
-    wb, we = plan0.win_ranges[rank]
-    lo0, hi0 = plan0.z_computed[rank]
-    vol0 = fetch_planes(lo0, hi0) if hi0 > lo0 else None
-    if we > wb:
-        q = _lib.SwParams.from_buffer_copy(params)
-        q.win_begin, q.win_end, q.z0, q.nz = wb, we, lo0, hi0 - lo0
-        mine = engine.window_max(q, vol0)
-    else:
-        mine = np.zeros(0, dtype=np.int32)
-    parts = [None] * world
-    dist.all_gather_object(parts, mine)
-    wmax = np.concatenate([np.asarray(x, dtype=np.int32) for x in parts])
+    firsts, mine = [], []
+    for eng, fetch, rank in zip(engines, fetchers, ranks):
+        wb, we = plan0.win_ranges[rank]
+        lo0, hi0 = plan0.z_computed[rank]
+        vol0 = fetch(lo0, hi0) if hi0 > lo0 else None
+        if we > wb:
+            q = _lib.SwParams.from_buffer_copy(params)
+            q.win_begin, q.win_end, q.z0, q.nz = wb, we, lo0, hi0 - lo0
+            mine.append(eng.window_max(q, vol0))
+        else:
+            mine.append(np.zeros(0, dtype=np.int32))
+        firsts.append((lo0, hi0, vol0))
+    wmax = np.concatenate([np.asarray(x, dtype=np.int32) for x in exchange(mine)])
     plan = plan_from_params(params, world, np.where(wmax > params.skip_threshold, 1.0, 0.02).astype(np.float32))
+    if check is not None:
+        check(plan)
+    return [(plan,) + _complete_slab(eng, fetch, plan, rank, Z, erode_iters, zblock, params, *first)
+            for eng, fetch, rank, first in zip(engines, fetchers, ranks, firsts)]
+
+
+def _complete_slab(engine, fetch_planes, plan, rank, Z, erode_iters, zblock, params, lo0, hi0, vol0):
+    """rank's final slab [lo, hi) of the volume, re-using the planes [lo0, hi0) fetched for the unweighted plan"""
+    import torch
+
     lo, hi = plan.slab(rank, Z, erode_iters, zblock)
     if hi <= lo:
-        return plan, lo, lo, torch.empty((0, int(params.Yp), int(params.Xp)), dtype=torch.uint16, device=engine.device)
+        return lo, lo, torch.empty((0, int(params.Yp), int(params.Xp)), dtype=torch.uint16, device=engine.device)
     vol = torch.empty((hi - lo, int(params.Yp), int(params.Xp)), dtype=torch.uint16, device=engine.device)
     have_lo, have_hi = (max(lo, lo0), min(hi, hi0)) if vol0 is not None else (lo, lo)
     if have_hi > have_lo:
@@ -191,7 +214,7 @@ def balanced_plan(engine, params, fetch_planes, world: int, rank: int, dist, Z: 
             vol[have_hi - lo:] = fetch_planes(have_hi, hi)
     else:
         vol[:] = fetch_planes(lo, hi)
-    return plan, lo, hi, vol
+    return lo, hi, vol
 
 
 def _needs_host_staging(t, dist) -> bool:

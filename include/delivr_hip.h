@@ -216,10 +216,19 @@ int dlv_comm_range_recover(dlv_comm* c, int* n_changed /* or NULL */);
  * call the planes a rank OWNS hold the complete sums: a neighbour's partial sum is added as one term, in increasing
  * source-rank order - the result is fixed by the plan and does not depend on arrival order; against the single-device
  * pass it is the same terms in another association (fp32 rounding; the count map is exact).  stats: [world] or NULL.
- * Synchronous. */
+ * Synchronous.  The planes a rank computed but does not own still hold its partial sums afterwards: a host that runs several
+ * passes into the same slabs zeroes them between the calls (the owner has added them).  Gaussian blend over several ranks
+ * with p->wsum_dev set: DLV_EINVAL (one buffer cannot be every rank's weight sums) - use dlv_sw_infer_sharded_wsum. */
 int dlv_sw_infer_sharded(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_plan* plan, const int* slab_z0, const int* slab_nz,
                          const uint16_t* const* vol_slab_dev, float* const* acc_slab_dev, uint8_t* const* cnt_slab_dev,
                          dlv_sw_stats* stats);
+/* dlv_sw_infer_sharded plus one fp32 (slab_nz[r],Yp,Xp) weight-sum slab per rank for the Gaussian blend (wsum_slab_dev[r] on
+ * devs[r], in/out; NULL: no weight sums); p->wsum_dev is ignored.  The seam exchange moves the weight sums beside the sums
+ * and the owner adds them in the same increasing source-rank order, so the planes a rank owns hold the complete weight sums
+ * too.  Constant mode ignores wsum_slab_dev.  Synchronous. */
+int dlv_sw_infer_sharded_wsum(dlv_comm* c, const dlv_sw_params* p, const dlv_shard_plan* plan, const int* slab_z0,
+                              const int* slab_nz, const uint16_t* const* vol_slab_dev, float* const* acc_slab_dev,
+                              uint8_t* const* cnt_slab_dev, float* const* wsum_slab_dev, dlv_sw_stats* stats);
 
 /* ---- finalize: divide, threshold, eroded re-mask ------------------------------------------- */
 /* inference/inference.py:285-299 + create_nifti_seg (:31-95).  mean = acc/cnt; cnt_dev == NULL: acc_dev already holds

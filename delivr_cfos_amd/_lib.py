@@ -80,6 +80,20 @@ class UnetWeights(C.Structure):
     ]
 
 
+class DebugLayerArgs(C.Structure):
+    """dlv_debug_layer_args (include/delivr_hip_diag.h): one layer of the 16-bit path through the test hook dlv_debug_layer16."""
+    _fields_ = [
+        ("kind", C.c_int), ("op", C.c_int), ("index", C.c_int),
+        ("in1", C.c_void_p), ("c1", C.c_int), ("ss1", C.c_void_p),
+        ("in2", C.c_void_p), ("c2", C.c_int),
+        ("vol", C.c_void_p), ("flip_dim", C.c_int),
+        ("out", C.c_void_p),
+        ("B", C.c_int), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("ran_zreg", C.c_int), ("ran_upconv", C.c_int), ("ran_stem", C.c_int), ("drops_bias", C.c_int),
+        ("drops_fold_const", C.c_int), ("raw_scale", C.c_float),
+    ]
+
+
 class SwParams(C.Structure):
     _fields_ = [
         ("Zp", C.c_int), ("Yp", C.c_int), ("Xp", C.c_int),
@@ -188,6 +202,7 @@ SIGNATURES = {
     "dlv_debug_set_format": (C.c_int, [_P, C.c_int]),
     "dlv_debug_layer_bf16": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                        C.c_int]),
+    "dlv_debug_layer16": (C.c_int, [_P, C.POINTER(DebugLayerArgs)]),
     "dlv_unet_set_conv_shift": (C.c_int, [_P, C.c_int, C.c_int]),
     "dlv_unet_get_conv_shift": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "dlv_unet_note_conv_shifts": (C.c_int, [_P, C.POINTER(C.c_int)]),

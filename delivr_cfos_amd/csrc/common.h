@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/delivr_hip.h"
+#include "../../include/delivr_hip_diag.h"  // (the layer test hook's report bits)
 
 #define DLV_WAVE 64
 #define DLV_MAX_LANES 6
@@ -133,6 +134,9 @@ struct dlv_ctx {
     int deep_mask = 2;       // conv_deep.hip: bit 0 = the layers the LDS-weights z-march also takes, bit 1 = the others
     int generic_ncb = 0;     // cout blocks per workgroup of the generic conv (0: its own choice)
     int zreg_dbg = 0;        // 1 = edge-step code on every plane of the z-reg conv
+    // what the last launches ran, for the layer test hook (dlv_debug_layer16): z-reg instantiation (DLV_DBG_ZR_* bits, 0 = none)
+    // and upconv kernel (1 = one tile per workgroup, 2 = persistent, 0 = none)
+    int ran_zreg = 0, ran_upconv = 0;
     int deep_small = 1;      // 0 = levels smaller than a tile of conv_deep.hip and its 32-output-channel layers take the generic conv (A/B)
     bool pool_rows_off = false, erode_xy_split = false, erode_z_two_sweeps = false, ccl_simple = false;
     bool resample_simple = false, resample_run16 = false;

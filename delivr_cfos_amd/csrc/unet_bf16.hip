@@ -299,13 +299,13 @@ __global__ void __launch_bounds__(256) stem_mfma_kernel(const uint16_t* __restri
     uint4 a[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) a[s] = AS_FRAG(wpk[s * 64 + lane]);
-    f32x16 bsv;  // the bias is the C operand of the first MFMA of every row
+    // No conv bias: the InstanceNorm that follows removes it, and statistics summed in fp32 without it stay exact where the
+    // raw output is (nearly) constant - a background window's raw output is the bias alone, whose E[x^2] - E[x]^2 in fp32
+    // left a variance of ~1e-6 b^2 (the scale 1.5e-3 off at eps 1e-5: tests/test_gpu_conv_kernels.py)
+    const f32x16 bsv = {};
     float ssum[16], ssq[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        bsv[r] = bias[(r & 3) + 8 * (r >> 2) + 4 * h] * P::STEM_SCALE;
-        ssum[r] = ssq[r] = 0.f;
-    }
+    for (int r = 0; r < 16; ++r) ssum[r] = ssq[r] = 0.f;
     float nsc[16], nsh[16];
     if (MODE == 2) {
 #pragma unroll
@@ -1795,55 +1795,126 @@ int pack_weights_16(dlv_ctx* ctx) {
 }
 
 template <class P>
-int debug_layer_16(dlv_ctx* ctx, int kind, int index, const float* in1_dev, int c1, const float* in2_dev, int c2,
-                   float* out_dev, int B, int D, int H, int W) {
-    const long long vox = (long long)D * H * W;
-    if (kind == 0 || kind == 2 || kind == 3) {  // 2: raw conv output (no InstanceNorm / Mish), 3: the layer's scale/shift pairs: kernel debugging
-        if (index < 1 || index >= DLV_N_CONV) return dlv_fail(ctx, DLV_EINVAL, "conv index must be 1..17");
-        const DlvConvLayer& L = ctx->conv[index];
-        if (c1 + c2 != L.cin || c1 % 32 || c2 % 32) return dlv_fail(ctx, DLV_EINVAL, "bad channel split");
-        const size_t b1 = (size_t)B * c1 * vox * 2, b2 = (size_t)B * c2 * vox * 2, bo = (size_t)B * L.cout * vox * 2;
-        const long long tiles = (long long)dlv_cdiv(D, 4) * dlv_cdiv(H, 4) * dlv_cdiv(W, 8);
-        const size_t pf = (size_t)B * tiles * L.cout * 2;
-        char* base;
-        DLV_TRY(dlv_ws_get(ctx, WS_BF16_ACT, b1 + b2 + bo + 1024, (void**)&base));
-        char* sbase;
-        DLV_TRY(dlv_ws_get(ctx, WS_STATS, pf * 4 + Net16<P>::ss_bytes(B) + 256, (void**)&sbase));
-        uint4 *i1 = (uint4*)base, *i2 = (uint4*)(base + ((b1 + 255) & ~(size_t)255)),
-              *o = (uint4*)(base + ((b1 + 255) & ~(size_t)255) + ((b2 + 255) & ~(size_t)255));
-        Net16<P> net{ctx, B, (float*)sbase, pf, (float2*)(sbase + ((pf * 4 + 255) & ~(size_t)255))};
-        const int g = net.grid1d(vox);
-        hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(g, c1 / 8, B), dim3(256), 0, ctx->stream, in1_dev, i1, c1, vox);
-        if (c2) hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(g, c2 / 8, B), dim3(256), 0, ctx->stream, in2_dev, i2, c2, vox);
-        typename Net16<P>::Act t1{i1, c1, nullptr}, t2{i2, c2, nullptr};
-        DLV_TRY(net.conv(index, t1, c2 ? &t2 : nullptr, o, Dims{D, H, W}));
-        if (kind == 0) DLV_TRY(net.norm_mish(o, L.cout, Dims{D, H, W}, nullptr, net.ss_of(index), true));
-        if (kind == 3) {
-            DLV_HIP(ctx, hipMemcpyAsync(out_dev, net.ss_of(index), (size_t)B * L.cout * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
-            return DLV_OK;
-        }
-        hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(g, L.cout / 8, B), dim3(256), 0, ctx->stream, o, out_dev, L.cout, vox);
-        DLV_LAUNCH_CHECK(ctx, "debug conv");
-        return DLV_OK;
-    }
+int debug_layer_16(dlv_ctx* ctx, dlv_debug_layer_args& a) {
+    const int B = a.B, D = a.D, H = a.H, W = a.W;
+    const Dims d{D, H, W};
+    const long long vox = d.vox();
+    a.ran_zreg = a.ran_upconv = a.ran_stem = a.drops_bias = a.drops_fold_const = 0;
+    a.raw_scale = 1.f;
+    ctx->ran_zreg = ctx->ran_upconv = 0;
+    if (B < 1 || D < 1 || H < 1 || W < 1) return dlv_fail(ctx, DLV_EINVAL, "debug layer: empty shape");
+    const int kind = a.kind;
     if (kind == 1) {
+        if (a.op != DLV_DBG_CONV) return dlv_fail(ctx, DLV_EINVAL, "kind 1 (deconv) runs as op 0 only");
+        const int index = a.index, c1 = a.c1;
         if (index < 0 || index >= DLV_N_DECONV) return dlv_fail(ctx, DLV_EINVAL, "deconv index must be 0..3");
         const DlvDeconvLayer& L = ctx->deconv[index];
-        if (c1 != L.cin || c2 != 0) return dlv_fail(ctx, DLV_EINVAL, "bad channels");
+        if (!a.in1 || c1 != L.cin || a.c2 != 0 || a.ss1) return dlv_fail(ctx, DLV_EINVAL, "bad channels");
         const size_t b1 = (size_t)B * c1 * vox * 2, bo = (size_t)B * L.cout * vox * 8 * 2;
         char* base;
         DLV_TRY(dlv_ws_get(ctx, WS_BF16_ACT, b1 + bo + 1024, (void**)&base));
         uint4 *i1 = (uint4*)base, *o = (uint4*)(base + ((b1 + 255) & ~(size_t)255));
         Net16<P> net{ctx, B, nullptr, 0, nullptr};
-        hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(net.grid1d(vox), c1 / 8, B), dim3(256), 0, ctx->stream, in1_dev, i1, c1, vox);
+        hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(net.grid1d(vox), c1 / 8, B), dim3(256), 0, ctx->stream, a.in1, i1, c1, vox);
         typename Net16<P>::Act t1{i1, c1, nullptr};
-        DLV_TRY(net.deconv(index, t1, o, Dims{D, H, W}));
-        hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(net.grid1d(vox * 8), L.cout / 8, B), dim3(256), 0, ctx->stream, o, out_dev,
+        DLV_TRY(net.deconv(index, t1, o, d));
+        hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(net.grid1d(vox * 8), L.cout / 8, B), dim3(256), 0, ctx->stream, o, a.out,
                            L.cout, vox * 8);
         DLV_LAUNCH_CHECK(ctx, "debug deconv");
         return DLV_OK;
     }
-    return dlv_fail(ctx, DLV_EINVAL, "kind must be 0 (conv block) or 1 (deconv)");
+    if (kind != 0 && kind != 2 && kind != 3) return dlv_fail(ctx, DLV_EINVAL, "kind must be 0 (final), 1 (deconv), 2 (raw) or 3 (scale/shift)");
+    // 2: raw conv output (no InstanceNorm / Mish), 3: the layer's scale/shift pairs
+    const int li = a.op == DLV_DBG_STEM ? 0 : a.index;
+    if (a.op == DLV_DBG_FOLDED && li != 16) return dlv_fail(ctx, DLV_EINVAL, "the folded conv is block 16");
+    if (a.op == DLV_DBG_CONV && (li < 1 || li >= DLV_N_CONV)) return dlv_fail(ctx, DLV_EINVAL, "conv index must be 1..17");
+    if (a.op < DLV_DBG_CONV || a.op > DLV_DBG_STEM) return dlv_fail(ctx, DLV_EINVAL, "op must be 0 (conv), 1 (folded) or 2 (stem)");
+    const DlvConvLayer& L = ctx->conv[li];
+    int c1 = a.c1, c2 = a.c2;
+    long long vox2 = vox;  // voxels of in2 (the coarse tensor of the folded conv)
+    if (a.op == DLV_DBG_STEM) {
+        if (!a.vol) return dlv_fail(ctx, DLV_EINVAL, "the stem reads vol");
+        if (a.flip_dim != -1 && (a.flip_dim < 2 || a.flip_dim > 4)) return dlv_fail(ctx, DLV_EINVAL, "flip_dim must be -1 or 2..4");
+        c1 = c2 = 0;
+    } else {
+        if (!a.in1) return dlv_fail(ctx, DLV_EINVAL, "in1 missing");
+        if (a.op == DLV_DBG_FOLDED) {
+            if (c1 != 32 || c2 != 32 || !a.in2 || D % 2 || H % 2 || W % 2) return dlv_fail(ctx, DLV_EINVAL, "folded conv: 32 fine + 32 coarse channels, even sizes");
+            vox2 = vox / 8;
+        } else if (c1 + c2 != L.cin || c1 % 32 || c2 % 32 || (c2 && !a.in2)) {
+            return dlv_fail(ctx, DLV_EINVAL, "bad channel split");
+        }
+    }
+    const bool folded = a.op == DLV_DBG_FOLDED;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b1 = (size_t)B * c1 * vox * 2, b2 = (size_t)B * c2 * vox2 * 2, bp = folded ? (size_t)B * 32 * vox * 2 : 0,
+                 bo = (size_t)B * L.cout * vox * 2, bst = (size_t)B * 3 * sizeof(int);
+    // partial sums: at most one row per 4 x 4 x 8 voxels (generic conv tiles; the z-march / z-reg / stem tiles are larger)
+    const long long tiles = (long long)dlv_cdiv(D, 4) * dlv_cdiv(H, 4) * dlv_cdiv(W, 8) + 64;
+    const size_t pf = (size_t)B * tiles * std::max(L.cout, 64) * 2;
+    char* base;
+    DLV_TRY(dlv_ws_get(ctx, WS_BF16_ACT, al(b1) + al(b2) + al(bp) + al(bo) + al(bst) + 1024, (void**)&base));
+    char* sbase;
+    DLV_TRY(dlv_ws_get(ctx, WS_STATS, al(pf * 4) + Net16<P>::ss_bytes(B) + 256, (void**)&sbase));
+    uint4 *i1 = (uint4*)base, *i2 = (uint4*)(base + al(b1)), *pb = (uint4*)(base + al(b1) + al(b2)),
+          *o = (uint4*)(base + al(b1) + al(b2) + al(bp));
+    int* starts = (int*)(base + al(b1) + al(b2) + al(bp) + al(bo));
+    Net16<P> net{ctx, B, (float*)sbase, pf, (float2*)(sbase + al(pf * 4))};
+    const int g = net.grid1d(vox);
+    if (c1) hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(g, c1 / 8, B), dim3(256), 0, ctx->stream, a.in1, i1, c1, vox);
+    if (c2) hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(net.grid1d(vox2), c2 / 8, B), dim3(256), 0, ctx->stream, a.in2, i2, c2, vox2);
+    DLV_LAUNCH_CHECK(ctx, "debug layer: f32_to_cp_kernel");
+    bool final_written = false;  // (the activating stem pass stores the final tensor itself)
+    if (a.op == DLV_DBG_STEM) {
+        // B windows of one (B*D, H, W) volume: window n starts at plane n * D
+        std::vector<int> st(3 * (size_t)B, 0);
+        for (int n = 0; n < B; ++n) st[3 * n] = n * D;
+        DLV_HIP(ctx, hipMemcpyAsync(starts, st.data(), bst, hipMemcpyHostToDevice, ctx->stream));
+        DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (st is a host temporary)
+        const int tY = dlv_cdiv(H, SM_TY), tX = dlv_cdiv(W, SM_TX), tZ = dlv_cdiv(D, SM_TZ * SM_ZC);
+        const dim3 grid(tZ * tY * tX, 1, B);
+        if ((size_t)B * grid.x * 64 > pf) return dlv_fail(ctx, DLV_ESTATE, "partials buffer too small (stem)");
+        const uint4* wst = reinterpret_cast<const uint4*>(wpack<P>(L));
+        const uint16_t* vol = reinterpret_cast<const uint16_t*>(a.vol);
+        if (kind == 2)  // raw tensor + statistics in one pass (the kernel's MODE 0)
+            hipLaunchKernelGGL((stem_mfma_kernel<P, 0>), grid, dim3(256), 0, ctx->stream, vol, H, W, starts, a.flip_dim, wst,
+                               L.bias16, o, net.partials, (const float2*)nullptr, D, H, W, tY, tX);
+        else  // what a forward runs: statistics pass, then (kind 0) the activating pass
+            hipLaunchKernelGGL((stem_mfma_kernel<P, 1>), grid, dim3(256), 0, ctx->stream, vol, H, W, starts, a.flip_dim, wst,
+                               L.bias16, o, net.partials, (const float2*)nullptr, D, H, W, tY, tX);
+        DLV_LAUNCH_CHECK(ctx, "debug stem_mfma_kernel");
+        DLV_TRY(net.stats((int)grid.x, 0, d));
+        if (kind == 0) {
+            hipLaunchKernelGGL((stem_mfma_kernel<P, 2>), grid, dim3(256), 0, ctx->stream, vol, H, W, starts, a.flip_dim, wst,
+                               L.bias16, o, net.partials, (const float2*)net.ss_of(0), D, H, W, tY, tX);
+            DLV_LAUNCH_CHECK(ctx, "debug stem_mfma_kernel<2>");
+            final_written = true;
+        }
+        a.ran_stem = 1;
+        a.drops_bias = 1;  // (stem_mfma_kernel adds no bias)
+        a.raw_scale = P::STEM_SCALE * exp2f(-(float)L.shift);
+    } else {
+        typename Net16<P>::Act t1{i1, c1, reinterpret_cast<const float2*>(a.ss1)}, t2{i2, c2, nullptr};
+        if (folded) {
+            if (!net.folds_up(16, 32, d)) return dlv_fail(ctx, DLV_EUNSUP, "debug layer: a forward does not fold block 16 at %dx%dx%d", D, H, W);
+            DLV_TRY(net.conv_folded(16, t1, t2, pb, o, d, Dims{D / 2, H / 2, W / 2}));
+            a.drops_fold_const = 1;
+        } else {
+            DLV_TRY(net.conv(li, t1, c2 ? &t2 : nullptr, o, d));
+        }
+        a.raw_scale = exp2f(-(float)L.shift);
+    }
+    a.ran_zreg = ctx->ran_zreg;
+    a.ran_upconv = ctx->ran_upconv;
+    a.drops_bias |= a.ran_zreg != 0;  // (the z-reg conv stores no conv bias: the InstanceNorm removes it)
+    if (kind == 3) {
+        DLV_HIP(ctx, hipMemcpyAsync(a.out, net.ss_of(li), (size_t)B * L.cout * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+        return DLV_OK;
+    }
+    if (kind == 0 && !final_written) DLV_TRY(net.norm_mish(o, L.cout, d, nullptr, net.ss_of(li), true));
+    hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(g, L.cout / 8, B), dim3(256), 0, ctx->stream, o, a.out, L.cout, vox);
+    DLV_LAUNCH_CHECK(ctx, "debug layer");
+    return DLV_OK;
 }
 
 }  // namespace
@@ -1913,13 +1984,32 @@ int dlv_unet_tiles_bf16(dlv_ctx* ctx, const uint16_t* vol, int Yp, int Xp, const
     return forward_16<PBf16>(ctx, nullptr, vol, Yp, Xp, starts_dev, flip_dim, scale, nullptr, acc, B, d, h, w);
 }
 
-// test hook: one conv block (raw conv + InstanceNorm + Mish) or one deconv of the 16-bit path on fp32
-// NCDHW tensors (converted on the device); precision DLV_PREC_BF16 or DLV_PREC_F16
-extern "C" int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev, int c1, const float* in2_dev,
-                                    int c2, float* out_dev, int B, int D, int H, int W) {
-    if (!ctx || !in1_dev || !out_dev) return DLV_EINVAL;
+// test hooks (include/delivr_hip_diag.h): one layer of the 16-bit path on fp32 NCDHW tensors (converted on the device) in the
+// format of dlv_debug_set_format.  dlv_debug_layer_bf16 is the older positional form of dlv_debug_layer16.
+extern "C" int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args) {
+    if (!ctx || !args || !args->out) return DLV_EINVAL;
     if (!ctx->weights_loaded) return dlv_fail(ctx, DLV_ESTATE, "no weights");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->debug_f16) return debug_layer_16<PF16>(ctx, kind, index, in1_dev, c1, in2_dev, c2, out_dev, B, D, H, W);
-    return debug_layer_16<PBf16>(ctx, kind, index, in1_dev, c1, in2_dev, c2, out_dev, B, D, H, W);
+    if (ctx->debug_f16) return debug_layer_16<PF16>(ctx, *args);
+    return debug_layer_16<PBf16>(ctx, *args);
+}
+
+extern "C" int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev, int c1, const float* in2_dev,
+                                    int c2, float* out_dev, int B, int D, int H, int W) {
+    if (!in1_dev) return DLV_EINVAL;
+    dlv_debug_layer_args a{};
+    a.kind = kind;
+    a.op = DLV_DBG_CONV;
+    a.index = index;
+    a.in1 = in1_dev;
+    a.c1 = c1;
+    a.in2 = in2_dev;
+    a.c2 = c2;
+    a.flip_dim = -1;
+    a.out = out_dev;
+    a.B = B;
+    a.D = D;
+    a.H = H;
+    a.W = W;
+    return dlv_debug_layer16(ctx, &a);
 }

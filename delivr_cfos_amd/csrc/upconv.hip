@@ -470,6 +470,7 @@ int dlv_upconv2_launch(dlv_ctx* ctx, bool f16, const void* in, const void* wpk, 
                        int cstride, int c0) {
     if (Wc % 2 || Dc <= 0 || Hc <= 0 || Wc <= 0) return dlv_fail(ctx, DLV_EUNSUP, "upconv: even coarse width expected");
     const int tilesX = dlv_cdiv(Wc, UC_TX), tilesY = dlv_cdiv(Hc, UC_TY), tilesZ = dlv_cdiv(Dc, UC_TZ);
+    ctx->ran_upconv = dlv_upconv2_persistent(ctx, Dc, Hc, Wc) ? 2 : 1;
     if (dlv_upconv2_persistent(ctx, Dc, Hc, Wc)) {
         static int ncu = 0;
         if (!ncu) DLV_HIP(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));

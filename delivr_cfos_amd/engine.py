@@ -364,6 +364,54 @@ class HipEngine:
         self._leave()
         return out
 
+    _BLOCK_COUT = (0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 5, 5)  # features[] index of each conv block's Cout
+
+    def debug_layer16(self, kind: int, op: str = "conv", index: int = 0, in1=None, ss1=None, in2=None, vol=None,
+                      flip_dim=None, precision: str = "bf16"):
+        """test hook (dlv_debug_layer16): one conv block (op "conv", in1 raw where ss1 = its (B, c1, 2) scale/shift is given),
+        the folded first conv of upcat_1 (op "folded": in1 fine skip tensor, in2 ACTIVATED coarse tensor) or the stem (op
+        "stem": vol = B uint16 windows (B, D, H, W)).  kind 0 final output, 2 raw output, 3 scale/shift (B, Cout, 2).
+        Returns (out, report): report names the kernels that ran and how the raw output is stored (delivr_hip_diag.h)."""
+        torch = self.torch
+        a = _lib.DebugLayerArgs()
+        a.kind, a.index, a.flip_dim = int(kind), int(index), -1 if flip_dim is None else int(flip_dim)
+        a.op = {"conv": 0, "folded": 1, "stem": 2}[op]
+        if op == "stem":
+            B, D, H, W = vol.shape
+            a.vol = self._dev(vol, torch.uint16, "vol").value
+            a.index = 0
+        else:
+            B, c1, D, H, W = in1.shape
+            a.in1, a.c1 = self._dev(in1, torch.float32, "in1").value, int(c1)
+            if in2 is not None:
+                a.in2, a.c2 = self._dev(in2, torch.float32, "in2").value, int(in2.shape[1])
+            if ss1 is not None:
+                if tuple(ss1.shape) != (B, c1, 2):
+                    raise ValueError(f"ss1: expected shape {(B, c1, 2)}, got {tuple(ss1.shape)}")
+                a.ss1 = self._dev(ss1, torch.float32, "ss1").value
+        if op == "folded":
+            a.index = 16
+        cout = self.features[self._BLOCK_COUT[a.index]] if op != "stem" else self.features[0]
+        shape = (B, cout, 2) if kind == 3 else (B, cout, D, H, W)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        a.out = self._dev(out, torch.float32, "out").value
+        a.B, a.D, a.H, a.W = int(B), int(D), int(H), int(W)
+        self._check(self.lib.dlv_debug_set_format(self.ctx, PREC_F16 if precision in ("fp16", "f16") else PREC_BF16_ALL))
+        self._enter()
+        self._check(self.lib.dlv_debug_layer16(self.ctx, C.byref(a)))
+        self._leave()
+        zr = a.ran_zreg
+        report = {
+            "zreg": None if not zr else "{}_c{}_t{}_{}".format("f16" if zr & 2 else "bf16", 64 if zr & 4 else 32, 16 if zr & 8 else 8,
+                                                              ("adda1" if zr & 16 else "add") if zr & 32 else ("a1" if zr & 16 else "a0")),
+            "upconv": {0: None, 1: "upconv2", 2: "upconv2m"}[a.ran_upconv],
+            "stem": bool(a.ran_stem),
+            "drops_bias": bool(a.drops_bias),
+            "drops_fold_const": bool(a.drops_fold_const),
+            "raw_scale": float(a.raw_scale),
+        }
+        return out, report
+
     # ---- sliding window ----------------------------------------------------------------------------
     def make_sw_params(self, padded_shape, roi, overlap=0.5, flip_dim=None, skip_threshold=0, precision="fp16",
                        sw_batch=0, win_range=None, slab=None, repeat=1, blend="constant", sigma_scale=0.125,

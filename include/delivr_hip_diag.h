@@ -47,6 +47,47 @@ int dlv_debug_set_format(dlv_ctx* ctx, int precision);
 int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev, int c1, const float* in2_dev,
                          int c2, float* out_dev, int B, int D, int H, int W);
 
+/* The layer test hook proper (dlv_debug_layer_bf16 forwards to it): one layer of the 16-bit path in the format of
+ * dlv_debug_set_format, through the same dispatch as a forward, on fp32 NCDHW device tensors.
+ *   op 0 (DLV_DBG_CONV)   kind 0/2/3: conv block `index` (1..17) on [in1 (c1), in2 (c2)]; ss1 (device float2 [B][c1], may be
+ *                         NULL): in1 is RAW and awaits InstanceNorm scale/shift ss1 + Mish - the dispatcher (fuse_layers /
+ *                         fuse_levels) decides whether the conv activates it while staging or a normalisation pass runs first.
+ *                         kind 1: transposed conv `index` (0..3) of in1 -> (B, Cout, 2D, 2H, 2W).
+ *   op 1 (DLV_DBG_FOLDED) the folded first conv of upcat_1 (block 16): in1 = fine skip tensor (B, 32, D, H, W), raw if ss1 is
+ *                         given, in2 = ACTIVATED coarse tensor (B, 32, D/2, H/2, W/2); DLV_EUNSUP where a forward would not fold.
+ *   op 2 (DLV_DBG_STEM)   block 0 from vol (device uint16 (B, D, H, W): B windows) flipped along flip_dim (2/3/4, -1 none)
+ *                         through the MFMA stem (kind 0: statistics pass + activating pass, kind 2/3: raw pass).
+ * kind 0: final output (B, Cout, D, H, W); 2: raw output in the stored scale (see below); 3: scale/shift pairs (float2 [B][Cout]).
+ * Reported: ran_zreg (DLV_DBG_ZR_* bits of the z-reg instantiation that ran, 0: another kernel), ran_upconv (1 one tile per
+ * workgroup, 2 persistent, 0 none), ran_stem (1: stem_mfma_kernel), and how the raw output relates to conv3d + bias:
+ *   raw = raw_scale * (conv3d(x, W) + (drops_bias ? 0 : bias) - (drops_fold_const ? sum_taps W_up * bias_up : 0))
+ * raw_scale = 2^-shift of the block (dlv_unet_set_conv_shift), times STEM_SCALE (2^-8 in fp16) for the stem. */
+#define DLV_DBG_CONV 0
+#define DLV_DBG_FOLDED 1
+#define DLV_DBG_STEM 2
+#define DLV_DBG_ZR_RAN 1
+#define DLV_DBG_ZR_F16 2
+#define DLV_DBG_ZR_C64 4
+#define DLV_DBG_ZR_T16 8
+#define DLV_DBG_ZR_ACT 16
+#define DLV_DBG_ZR_ADD 32
+typedef struct dlv_debug_layer_args {
+    int kind, op, index;
+    const float* in1;
+    int c1;
+    const float* ss1;
+    const float* in2;
+    int c2;
+    const unsigned short* vol;
+    int flip_dim;
+    float* out;
+    int B, D, H, W;
+    /* reported */
+    int ran_zreg, ran_upconv, ran_stem, drops_bias, drops_fold_const;
+    float raw_scale;
+} dlv_debug_layer_args;
+int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,14 +49,16 @@ CONV_CASES = [
     (9, 256, 0, 4, 4, 8),      # 256 -> 256 (NCB 4), TX 8
     (10, 128, 128, 2, 6, 12),  # concat 128+128 -> 128, odd sizes
     (12, 64, 64, 4, 8, 16),
-    # W >= 32 and Cout = 32: the z-marching kernel (ragged tiles, z segments, concat)
-    (1, 32, 0, 6, 12, 40),
-    (17, 32, 0, 40, 16, 64),
-    (16, 32, 32, 9, 8, 32),
-    (14, 32, 32, 24, 20, 72),
-    # Cout = 64 with W >= 32: z-march with two output-channel blocks (z segments, ragged rows)
-    (4, 32, 0, 20, 12, 32),
-    (5, 64, 0, 33, 24, 64),
+    # W >= 32 and Cout = 32 (ragged tiles, z segments, concat).  Layers of at most 32768 voxels take the LDS-weights
+    # z-march (conv_zmarch.hip), larger ones the register-resident-weights conv (conv_zreg_kernel.h, 8-row tiles here;
+    # every instantiation of it: tests/test_gpu_conv_kernels.py)
+    (1, 32, 0, 6, 12, 40),     # conv_zmarch.hip
+    (17, 32, 0, 40, 16, 64),   # z-reg c32_t8
+    (16, 32, 32, 9, 8, 32),    # conv_zmarch.hip
+    (14, 32, 32, 24, 20, 72),  # z-reg c64_t8 (32 + 32)
+    # Cout = 64 with W >= 32: two output-channel blocks (z segments, ragged rows)
+    (4, 32, 0, 20, 12, 32),    # conv_zmarch.hip
+    (5, 64, 0, 33, 24, 64),    # z-reg c64_t8
 ]
 
 

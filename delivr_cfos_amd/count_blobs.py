@@ -14,7 +14,7 @@ import pickle
 import numpy as np
 
 from . import hostio
-from .hostlogic import cells_csv_bytes, csv_name
+from .hostlogic import cells_csv_bytes, csv_name, size_filter_bounds
 
 
 def _find_cached(path: str, suffix: str, brain: str):
@@ -54,19 +54,83 @@ def _even_slabs(Z: int, world: int):
     return [(cuts[r], cuts[r + 1]) for r in range(world)]
 
 
-def _count_blobs_sharded(eng, bin_img, dist, path_out, brain):
+def _filter_active(bounds) -> bool:
+    """bounds: hostlogic.size_filter_bounds' answer - the filter removes something only with the switch on and a bound given"""
+    return bounds is not None and (bounds[0] >= 0 or bounds[1] >= 0)
+
+
+def _keep_mask(counts: np.ndarray, bounds) -> np.ndarray:
+    """the labels dlv_cc_size_filter_dev keeps, from their voxel counts (host side of the sharded path and of last_filter)"""
+    keep = np.ones(len(counts), dtype=bool)
+    if bounds[0] >= 0:
+        keep &= counts >= bounds[0]
+    if bounds[1] >= 0:
+        keep &= counts <= bounds[1]
+    keep[0] = False
+    return keep
+
+
+def _note_filter(bounds, n_before: int, n_kept: int, voxels_removed: int, quiet: bool = False):
+    count_blobs.last_filter = {"min_size": int(bounds[0]), "max_size": int(bounds[1]), "n_before": int(n_before), "n_kept": int(n_kept),
+                               "voxels_removed": int(voxels_removed)}
+    if not quiet:
+        print(f"size filter (min_size {bounds[0]}, max_size {bounds[1]}): kept {n_kept} of {n_before} components, "
+              f"removed {voxels_removed} voxels")
+
+
+def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None):
     """One process per GPU: every rank labels a Z-slab of the mask, seams are merged (parallel.ccl_sharded) and every
     rank writes ITS label slab straight into the output .npy (rank 0 creates the file once N - and with it the label
     dtype - is known); only the merged statistics travel to rank 0.  No rank ever holds the whole label volume (17 GB for
-    1024x2048x2048).  Returns (N, stats | None)."""
-    from .parallel import ccl_sharded
+    1024x2048x2048).  bounds: the size filter (hostlogic.size_filter_bounds) - every rank counts the voxels of the global
+    labels in its slab, the counts are summed over the ranks, every rank applies the same filter to its slab and the
+    statistics are taken on the filtered labels.  Returns (N, stats | None)."""
+    from .parallel import ccl_sharded, merge_stats
 
     rank, world = dist.get_rank(), dist.get_world_size()
     Z, Y, X = bin_img.shape
     slabs = _even_slabs(Z, world)
     lo, hi = slabs[rank]
     slab = hostio.upload(eng, bin_img[lo:hi], what="h2d_mask") if hi > lo else None
-    labels, N, stats = ccl_sharded(eng, slab, slabs, rank, dist, (Z, Y, X))
+    if not _filter_active(bounds):
+        labels, N, stats = ccl_sharded(eng, slab, slabs, rank, dist, (Z, Y, X))
+    else:
+        labels, n_before, _ = ccl_sharded(eng, slab, slabs, rank, dist, (Z, Y, X), want_stats=False)
+        # a rank that fails here must not leave the others waiting in the next collective: the error text travels with the
+        # counts, and the outcome of the filter is exchanged before the statistics are gathered (as for the slab writes below)
+        mine, failed = None, None
+        try:
+            if labels is not None:
+                mine = eng.cc_counts(labels, n_before).cpu().numpy().view(np.uint32)
+        except Exception as exc:
+            failed = f"rank {rank}: {exc!r}"
+        parts = [None] * world
+        dist.all_gather_object(parts, (mine, failed))
+        bad = [f for _, f in parts if f]
+        if bad:
+            raise RuntimeError("count_blobs: counting the voxels per label failed: " + "; ".join(bad))
+        total = np.zeros(n_before + 1, dtype=np.uint64)
+        for part, _ in parts:
+            if part is not None:
+                total += part
+        keep = _keep_mask(total, bounds)
+        N = int(keep.sum())
+        raw, failed = None, None
+        try:
+            if labels is not None:
+                kept = eng.cc_size_filter(labels, n_before, bounds[0], bounds[1], counts=np.minimum(total, 2**32 - 1).astype(np.uint32))
+                if kept != N:
+                    raise RuntimeError(f"kept {kept} components, the summed counts say {N}")
+                raw = eng.cc_stats_raw(labels, N)
+        except Exception as exc:
+            failed = f"rank {rank}: {exc!r}"
+        _raise_if_any_failed(dist, failed, "count_blobs: the size filter")
+        _note_filter(bounds, n_before, N, int(total[1:][~keep[1:]].sum()), quiet=rank != 0)
+        raws = [None] * world
+        dist.gather_object(raw, raws if rank == 0 else None, dst=0)
+        stats = None
+        if rank == 0:  # (the labels are global and final already: identity tables)
+            stats = merge_stats([np.arange(N + 1, dtype=np.uint32)] * world, raws, [s[0] for s in slabs], (Z, Y, X), N)
     out_path = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
     err = [None]
     if rank == 0:
@@ -110,8 +174,21 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     ranks along z; rank 0 writes the statistics and the CSV, every rank writes its slab of the labels and returns N.
     Rank 0 alone looks for a cached labelling and tells the others which branch to take, so the ranks cannot disagree
     about the collectives that follow (different cache views on a shared file system); a failure on rank 0 reaches the
-    other ranks as an error instead of a hang."""
+    other ranks as an error instead of a hang.
+
+    ``min_size`` / ``max_size``: ignored, as the reference ignores them, unless ``settings["mi355x"]["size_filter"]`` is true.
+    Then a component is kept when min_size <= voxels <= max_size (inclusive; a negative bound is no bound), the survivors are
+    renumbered 1..K in the order they had and everything written - label file, its name and dtype, statistics, CSV - is what
+    the mask without the removed components would have given; ``count_blobs.last_filter`` holds the numbers.  A cached label
+    file is reused as it is: the bounds are NOT re-applied to it.  A mask that needs the slab-streamed path (larger than the
+    HBM budget) is refused with the filter on."""
     from .engine import shared_engine
+
+    bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
+    count_blobs.last_filter = None  # set by a run that filtered
+    if bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
+        print(f"min_size {min_size} / max_size {max_size} are ignored, as in the reference; "
+              "settings['mi355x']['size_filter'] = true applies them")
 
     try:
         import torch.distributed as dist
@@ -144,7 +221,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
             raise RuntimeError(f"count_blobs: rank 0 failed while looking for a cached labelling: {branch[0][1]}")
         if not branch[0][1]:
             try:
-                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain)
+                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds)
             finally:
                 if own:
                     eng.close()
@@ -175,7 +252,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     try:
         import time
 
-        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start)
+        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
@@ -198,10 +275,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start):
+def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
-    made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into."""
+    made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
+    filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write."""
     import time
 
     labels_dev = None
@@ -224,6 +302,10 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start):
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
             plane = int(bin_img.shape[1]) * int(bin_img.shape[2]) * ccl_bytes_per_voxel()
             n_slabs = -(-need // max(budget, 1))
+            if _filter_active(bounds):
+                raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['size_filter'] needs the mask and its labels in HBM "
+                                  f"({need / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling "
+                                  "does not filter; raise settings['mi355x']['hbm_budget_gb'] or switch size_filter off")
             if plane > budget or n_slabs > bin_img.shape[0]:
                 raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): one mask plane with its labels and scratch needs {plane / 2**20:.1f} MiB, "
                                   f"the HBM budget is {budget / 2**20:.1f} MiB; raise settings['mi355x']['hbm_budget_gb']")
@@ -253,6 +335,14 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start):
             labels_dev, N = eng.ccl26(mask_dev)
             del mask_dev
             mark("ccl26")
+            if _filter_active(bounds):
+                n_before = N
+                counts_dev = eng.cc_counts(labels_dev, N)
+                N = eng.cc_size_filter(labels_dev, N, bounds[0], bounds[1], counts=counts_dev)
+                counts = counts_dev.cpu().numpy().view(np.uint32).astype(np.uint64)
+                _note_filter(bounds, n_before, N, int(counts[1:][~_keep_mask(counts, bounds)[1:]].sum()))
+                del counts_dev
+                mark("size_filter")
             final = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
             # (written as <name>.partial and renamed: never a partly written file under the cache's name) - by a side thread that
             # touches torch's copy stream only, never the context, while this thread goes on to the statistics and the CSV
@@ -274,6 +364,8 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start):
         else:
             N = int(cached.split("/")[-1].split("-")[1])
             print(f"Cached brain found at {cached} with {N} components, loading...")
+            if _filter_active(bounds):
+                print(f"size filter: the cached labelling is reused as it is, min_size {bounds[0]} / max_size {bounds[1]} are not applied to it")
             labels = np.load(cached, mmap_mode="r")
         mid = datetime.datetime.now()
         print(f"{mid} labelling+writing/loading took {mid - start} : {N}")
@@ -311,5 +403,6 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start):
     finally:
         if own:
             eng.close()
-    # note: size filtering happens later in the reference too (count_blobs.py:105)
+    # note: the reference takes min_size / max_size and never reads them (count_blobs.py:105); here they apply with
+    # settings["mi355x"]["size_filter"] (above, right after the labelling)
     return N, stats, wait

@@ -613,8 +613,15 @@ __global__ void __launch_bounds__(256) seam_pairs_kernel(const u32* __restrict__
     }
 }
 
-__global__ void __launch_bounds__(256) relabel_lut_kernel(u32* __restrict__ labels, u64 n, const u32* __restrict__ lut) {
-    // 4 labels per thread (16-byte accesses); background (0) maps to lut[0] = 0 without a table read
+__global__ void __launch_bounds__(256) relabel_lut_kernel(u32* __restrict__ labels, u64 n, const u32* __restrict__ lut, u32 head) {
+    // 4 labels per thread (16-byte accesses); background (0) maps to lut[0] = 0 without a table read.  head (< 4): the labels in
+    // front of the first 16-byte boundary of a volume that does not start on one - they and the tail go one by one
+    if (blockIdx.x == 0 && threadIdx.x >= 4 && threadIdx.x - 4 < head) {
+        const u32 l = labels[threadIdx.x - 4];
+        if (l) labels[threadIdx.x - 4] = lut[l];
+    }
+    labels += head;
+    n -= head;
     const u64 n4 = n / 4;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (u64)gridDim.x * blockDim.x) {
         uint4 v = reinterpret_cast<uint4*>(labels)[i];
@@ -631,6 +638,107 @@ __global__ void __launch_bounds__(256) relabel_lut_kernel(u32* __restrict__ labe
         const u32 l = labels[i];
         if (l) labels[i] = lut[l];
     }
+}
+
+// ---- size filter (count_blobs' min_size / max_size; cc3d.dust): voxel count per label, keep flags, order-preserving
+// renumbering of the kept labels through a lookup table ----------------------------------------------------------
+// cc_stats_kernel's aggregation with ONE atomic per (wave, label) instead of ten: a thread folds the runs of equal labels in
+// its 8 voxels, the lanes of a wave that hold the same label add up with shuffles and one lane issues the atomicAdd.  The
+// volume is walked as a flat array in tiles of 2048 voxels (a thread takes voxels [4t, 4t+4) and [1024 + 4t, 1024 + 4t + 4)
+// of the tile: every 16-byte load instruction of a wave covers one contiguous KiB); the last partial tile, and every tile of a
+// volume that does not start on a 16-byte boundary, is read label by label.  Labels above n are not counted (the table has
+// n + 1 rows); 0xffffffff stands for "no voxel".
+constexpr int CPT = 8;             // voxels per thread
+constexpr int CTILE = 256 * CPT;   // voxels per workgroup and sweep
+
+__device__ __forceinline__ void cc_counts_fold(const u32 (&l)[CPT], u32 n, u32* __restrict__ counts, u32& nbg) {
+    const int lane = threadIdx.x & 63;
+    // bit k of chg: voxel k starts a run (differs from the voxel before it); bit k of fgm: voxel k holds a label 1..n
+    unsigned fgm = 0, chg = 1u | (1u << CPT);
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+        nbg += l[k] == 0 ? 1u : 0u;
+        fgm |= ((l[k] != 0 && l[k] <= n) ? 1u : 0u) << k;
+        if (k > 0) chg |= (l[k] != l[k - 1] ? 1u : 0u) << k;
+    }
+    unsigned starts = fgm & chg;  // first voxels of this thread's foreground runs
+    if (!__any(starts != 0)) return;  // (wave-uniform) nothing but background in this wave's 512 voxels
+    while (true) {
+        const bool have = starts != 0;
+        if (!__any(have)) break;
+        u32 lab = 0, cnt = 0;
+        if (have) {
+            const int k0 = __ffs((int)starts) - 1;
+            starts &= starts - 1;
+            cnt = (u32)(__ffs((int)(chg >> (k0 + 1))) - 1) + 1u;  // up to the next run's start (bit CPT ends the last one)
+            lab = l[0];
+#pragma unroll
+            for (int k = 1; k < CPT; ++k) lab = (k0 == k) ? l[k] : lab;  // (no dynamic index into the registers)
+        }
+        // lanes holding the same label are combined; one leader per distinct label issues the atomic
+        bool pending = have;
+        while (true) {
+            const unsigned long long m = __ballot(pending);
+            if (!m) break;
+            const int leader = __ffsll((long long)m) - 1;
+            const u32 L = __shfl(lab, leader, 64);
+            const bool mine = pending && lab == L;
+            u32 c = mine ? cnt : 0;
+            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+            if (lane == leader) atomicAdd(counts + L, c);
+            pending = pending && !mine;
+        }
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) cc_counts_kernel(const u32* __restrict__ labels, u64 nvox, u32 n, u32* __restrict__ counts) {
+    const u64 ntiles = nvox / CTILE;
+    u32 nbg = 0;
+    u32 l[CPT];
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (workgroup-uniform trip count: the shuffles are convergent)
+        const u64 base = tile * CTILE + 4u * threadIdx.x;
+        if (VEC) {
+            typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
+            const u32x4_t u0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(labels + base));
+            const u32x4_t u1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(labels + base + CTILE / 2));
+            l[0] = u0.x; l[1] = u0.y; l[2] = u0.z; l[3] = u0.w;
+            l[4] = u1.x; l[5] = u1.y; l[6] = u1.z; l[7] = u1.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                l[k] = labels[base + k];
+                l[4 + k] = labels[base + CTILE / 2 + k];
+            }
+        }
+        cc_counts_fold(l, n, counts, nbg);
+    }
+    if (blockIdx.x == gridDim.x - 1 && ntiles * CTILE < nvox) {  // the last partial tile
+        const u64 base = ntiles * CTILE + (u64)threadIdx.x * CPT;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) l[k] = base + k < nvox ? labels[base + k] : 0xffffffffu;
+        cc_counts_fold(l, n, counts, nbg);
+    }
+    for (int o = 32; o > 0; o >>= 1) nbg += __shfl_xor(nbg, o, 64);
+    if ((threadIdx.x & 63) == 0 && nbg) atomicAdd(counts, nbg);
+}
+
+// The lookup table of the size filter is made in three launches over the same n + 1 rows, in this order: size_keep_kernel writes
+// the keep flags, the ccl_scan_* kernels turn them into their exclusive prefix sum (the number of kept labels below each label),
+// size_lut_kernel turns that into the new label.  Both kernels ask size_keeps(), so that they cannot disagree about a label.
+__device__ __forceinline__ bool size_keeps(const u32* __restrict__ counts, u64 l, u64 lo, u64 hi) {
+    // label 1..n whose voxel count lies in [lo, hi]; label 0 is the background: never kept
+    const u64 c = counts[l];
+    return l > 0 && c >= lo && c <= hi;
+}
+__global__ void __launch_bounds__(256) size_keep_kernel(const u32* __restrict__ counts, u64 rows, u64 lo, u64 hi, u32* __restrict__ keep) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (u64)gridDim.x * blockDim.x)
+        keep[i] = size_keeps(counts, i, lo, hi) ? 1u : 0u;
+}
+// lut[l] holds the exclusive scan of the flags: a kept label becomes that + 1, the others 0
+__global__ void __launch_bounds__(256) size_lut_kernel(const u32* __restrict__ counts, u64 rows, u64 lo, u64 hi, u32* __restrict__ lut) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (u64)gridDim.x * blockDim.x)
+        lut[i] = size_keeps(counts, i, lo, hi) ? lut[i] + 1u : 0u;
 }
 
 // shared by dlv_cc_stats_dev / dlv_cc_stats_raw_dev: raw per-label accumulators copied to the host
@@ -816,8 +924,71 @@ int dlv_relabel_u32_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, const
     if ((uintptr_t)labels_dev & 15) return dlv_fail(ctx, DLV_EINVAL, "labels must be 16-byte aligned");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     const int gs = (int)std::min<u64>((nvox / 4 + 255) / 256 + 1, (u64)256 * 32);
-    hipLaunchKernelGGL(relabel_lut_kernel, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, lut_dev);
+    hipLaunchKernelGGL(relabel_lut_kernel, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, lut_dev, 0u);
     DLV_LAUNCH_CHECK(ctx, "relabel_lut_kernel");
+    return DLV_OK;
+}
+
+int dlv_cc_counts_dev(dlv_ctx* ctx, const uint32_t* labels_dev, uint64_t nvox, uint64_t n, uint32_t* counts_dev) {
+    if (!ctx || !labels_dev || !counts_dev) return DLV_EINVAL;
+    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_counts: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "labels must be 4-byte aligned");
+    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    DLV_HIP(ctx, hipMemsetAsync(counts_dev, 0, ((size_t)n + 1) * 4, ctx->stream));
+    if (nvox == 0) return DLV_OK;
+    const int gs = (int)std::min<u64>(std::max<u64>(nvox / CTILE, 1), (u64)256 * 32);
+    DlvProf pr(ctx, "cc_counts", 0.0, (double)nvox * 4);
+    if (((uintptr_t)labels_dev & 15) == 0)
+        hipLaunchKernelGGL(cc_counts_kernel<true>, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, (u32)n, counts_dev);
+    else
+        hipLaunchKernelGGL(cc_counts_kernel<false>, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, (u32)n, counts_dev);
+    pr.end();
+    DLV_LAUNCH_CHECK(ctx, "cc_counts_kernel");
+    return DLV_OK;
+}
+
+int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, uint64_t n, const uint32_t* counts_dev,
+                           int64_t min_size, int64_t max_size, uint64_t* n_kept_out) {
+    if (!ctx || !labels_dev || !counts_dev || !n_kept_out) return DLV_EINVAL;
+    if (min_size >= 0 && max_size >= 0 && min_size > max_size)
+        return dlv_fail(ctx, DLV_EINVAL, "size filter: min_size %lld > max_size %lld", (long long)min_size, (long long)max_size);
+    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "size filter: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "labels must be 4-byte aligned");
+    *n_kept_out = n;
+    if (min_size < 0 && max_size < 0) return DLV_OK;  // no bound: nothing to do
+    if (n == 0 || nvox == 0) return DLV_OK;           // no component: nothing to remove
+    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    const u64 lo = min_size < 0 ? 0ull : (u64)min_size, hi = max_size < 0 ? ~0ull : (u64)max_size;
+    const u64 rows = n + 1, ng = (rows + SGRP - 1) / SGRP;
+    // scratch: the lookup table (n + 1 labels), the sums of its 1024-label groups, the number of kept labels
+    const size_t gsum_off = ((size_t)rows * 4 + 255) & ~(size_t)255;
+    const size_t total_off = (gsum_off + (size_t)(ng + 1) * 4 + 255) & ~(size_t)255;
+    char* ws;
+    DLV_TRY(dlv_ws_get(ctx, WS_MISC, total_off + 256, (void**)&ws));
+    u32* lut = (u32*)ws;
+    u32* gsum = (u32*)(ws + gsum_off);
+    u32* total = (u32*)(ws + total_off);
+    // bytes: the volume is read and (where it holds foreground) written back; the table lookups stay in the caches
+    DlvProf pr(ctx, "cc_size_filter", 0.0, (double)nvox * 8 + (double)rows * 20);
+    const int gr = (int)std::min<u64>((rows + 255) / 256, (u64)256 * 32);
+    hipLaunchKernelGGL(size_keep_kernel, dim3(gr), dim3(256), 0, ctx->stream, counts_dev, rows, lo, hi, lut);
+    DLV_LAUNCH_CHECK(ctx, "size_keep_kernel");
+    // exclusive scan of the flags with the three kernels of the labelling's renumbering (any number of labels)
+    hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, lut, rows, gsum);
+    hipLaunchKernelGGL(ccl_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, gsum, ng, total);
+    hipLaunchKernelGGL(ccl_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, lut, rows, gsum);
+    DLV_LAUNCH_CHECK(ctx, "ccl_scan_counts_kernel");
+    hipLaunchKernelGGL(size_lut_kernel, dim3(gr), dim3(256), 0, ctx->stream, counts_dev, rows, lo, hi, lut);
+    DLV_LAUNCH_CHECK(ctx, "size_lut_kernel");
+    const u32 head = (u32)std::min<u64>(((16 - ((uintptr_t)labels_dev & 15)) & 15) / 4, nvox);
+    const int gs = (int)std::min<u64>((nvox / 4 + 255) / 256 + 1, (u64)256 * 32);
+    hipLaunchKernelGGL(relabel_lut_kernel, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, lut, head);
+    DLV_LAUNCH_CHECK(ctx, "relabel_lut_kernel");
+    pr.end();
+    u32 kept = 0;
+    DLV_HIP(ctx, hipMemcpyAsync(&kept, total, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_kept_out = kept;
     return DLV_OK;
 }
 

@@ -601,6 +601,40 @@ class HipEngine:
         self._leave()
         self.sync()
 
+    def cc_counts(self, labels, n: int):
+        """Voxels per label 0..n of a label volume in HBM (dlv_cc_counts_dev) -> int32 tensor (uint32 payload) of n+1 in HBM."""
+        torch = self.torch
+        ptr = self._dev(labels, torch.int32, "labels")
+        counts = torch.empty(int(n) + 1, dtype=torch.int32, device=self.device)
+        self._enter()
+        self._check(self.lib.dlv_cc_counts_dev(self.ctx, ptr, int(labels.numel()), int(n), C.c_void_p(counts.data_ptr())))
+        self._leave()
+        return counts
+
+    def cc_size_filter(self, labels, n: int, min_size: int, max_size: int, counts=None) -> int:
+        """Size filter in place (dlv_cc_size_filter_dev): labels with min_size <= voxels <= max_size (inclusive, negative = no
+        bound) are renumbered 1..K in their order, the others become 0 -> K.  counts: the voxel counts of the labels 0..n when they
+        are not those of `labels` alone (a slab of a sharded run passes the sums over all slabs); a device tensor or an array."""
+        torch = self.torch
+        lo, hi = int(min_size), int(max_size)
+        if lo >= 0 and hi >= 0 and lo > hi:
+            raise ValueError(f"size filter: min_size {lo} > max_size {hi}")
+        ptr = self._dev(labels, torch.int32, "labels")
+        if lo < 0 and hi < 0:
+            return int(n)
+        if counts is None:
+            counts = self.cc_counts(labels, n)
+        elif not isinstance(counts, torch.Tensor):
+            counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.uint32).view(np.int32)).to(self.device)
+        if counts.device != self.device or counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() != int(n) + 1:
+            raise ValueError(f"counts: expected {int(n) + 1} contiguous int32 values (uint32 payload) on {self.device}")
+        kept = C.c_uint64()
+        self._enter()
+        self._check(self.lib.dlv_cc_size_filter_dev(self.ctx, ptr, int(labels.numel()), int(n), C.c_void_p(counts.data_ptr()),
+                                                    lo, hi, C.byref(kept)))
+        self._leave()
+        return int(kept.value)
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

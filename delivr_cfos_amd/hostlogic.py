@@ -67,6 +67,20 @@ def resolve_devices(cuda_devices, setting, device_count: int, group_world: int =
     return devs
 
 
+def size_filter_bounds(settings, min_size, max_size) -> Optional[Tuple[int, int]]:
+    """count_blobs' size filter: None when settings["mi355x"]["size_filter"] is absent or false (the reference accepts
+    min_size / max_size and ignores them, and so does count_blobs then), else (lo, hi): a component is kept when
+    lo <= voxels <= hi, both inclusive; a negative bound (returned as -1) is no bound, (-1, -1) keeps everything.
+    Raises ValueError for min_size > max_size with both >= 0 - only with the switch on: off, the bounds are not looked at."""
+    if not ((settings or {}).get("mi355x") or {}).get("size_filter"):
+        return None
+    lo = -1 if min_size is None else max(int(min_size), -1)
+    hi = -1 if max_size is None else max(int(max_size), -1)
+    if lo >= 0 and hi >= 0 and lo > hi:
+        raise ValueError(f"count_blobs: min_size {lo} > max_size {hi} keeps no component (settings['mi355x']['size_filter'] is on)")
+    return lo, hi
+
+
 def pass_schedule(tta: bool) -> List[Tuple[Optional[int], int]]:
     """(flip_dim, repeat) per DISTINCT pass.  The reference runs 1 plain pass, then 4 x {noise,
     noise + flip Z (dim 2), noise + flip Y (dim 3)} (inference/inference.py:261-279); its noise is

@@ -287,6 +287,18 @@ int dlv_seam_pairs_dev(dlv_ctx* ctx, const uint32_t* plane_a_dev, const uint32_t
 int dlv_relabel_u32_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, const uint32_t* lut_dev, uint64_t lut_len);
 int dlv_cc_stats_raw_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, uint32_t* counts,
                          uint32_t* bbmin, uint32_t* bbmax, uint64_t* sums);
+/* Size filter on a label volume (what cc3d users know as cc3d.dust; count_blobs' min_size / max_size).  The reference has no
+ * counterpart: it accepts the two bounds and ignores them.  Two calls, so that a sharded run can add up the counts of its
+ * slabs in between.  labels_dev: nvox uint32 labels 0..n, 4-byte aligned (16-byte aligned volumes take the 16-byte path).
+ *  dlv_cc_counts_dev: counts_dev[l] = number of voxels with label l, for l = 0..n (device array of n+1 uint32; labels above
+ *    n are not counted).  Asynchronous on the context's stream.
+ *  dlv_cc_size_filter_dev: label l >= 1 is kept when min_size <= counts_dev[l] <= max_size (both inclusive; a negative
+ *    bound is no bound).  The kept labels are renumbered 1..K in the order they had, the others become 0, in place: the
+ *    volume is the labelling of the mask without the removed components.  *n_kept_out = K.  Both bounds negative: K = n and
+ *    nothing is touched; min_size > max_size with both >= 0: DLV_EINVAL.  Synchronous. */
+int dlv_cc_counts_dev(dlv_ctx* ctx, const uint32_t* labels_dev, uint64_t nvox, uint64_t n, uint32_t* counts_dev);
+int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, uint64_t n, const uint32_t* counts_dev,
+                           int64_t min_size, int64_t max_size, uint64_t* n_kept_out);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

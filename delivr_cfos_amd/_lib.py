@@ -94,6 +94,33 @@ class DebugLayerArgs(C.Structure):
     ]
 
 
+PLAN_MAX_LABELS = 96
+# dlv_plan_conv.kernel / dlv_plan_deconv.kernel (include/delivr_hip_diag.h: DLV_PLAN_*); -1 = not launched
+PLAN_CONV_KERNELS = ("ZREG", "DEEP", "ZMARCH", "GENERIC", "STEM_MFMA", "STEM_VALU")
+PLAN_DECONV_KERNELS = ("DEEP", "REGW", "WST", "ROWS", "PARITY")
+
+
+class PlanConv(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("level", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("folded", C.c_int),
+                ("tile_rows", C.c_int), ("act_on_load", C.c_int), ("tx", C.c_int), ("ncb", C.c_int), ("wlds", C.c_int),
+                ("max_parts", C.c_longlong)]
+
+
+class PlanDeconv(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("norm_first", C.c_int), ("padded", C.c_int)]
+
+
+class PlanPool(C.Structure):
+    _fields_ = [("rows", C.c_int), ("writeback", C.c_int), ("norm_after", C.c_int), ("nt", C.c_int)]
+
+
+class LayerPlan(C.Structure):
+    """dlv_layer_plan (include/delivr_hip_diag.h): the kernels of one forward, from dlv_diag_plan (host arithmetic only)."""
+    _fields_ = [("conv", PlanConv * N_CONV), ("deconv", PlanDeconv * N_DECONV), ("pool", PlanPool * 4), ("n_labels", C.c_int),
+                ("labels", (C.c_char * 48) * PLAN_MAX_LABELS), ("flops", C.c_double * PLAN_MAX_LABELS),
+                ("bytes", C.c_double * PLAN_MAX_LABELS)]
+
+
 class SwParams(C.Structure):
     _fields_ = [
         ("Zp", C.c_int), ("Yp", C.c_int), ("Xp", C.c_int),
@@ -197,6 +224,8 @@ SIGNATURES = {
     "dlv_tiff_stack_to_device": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_longlong,
                                             C.c_longlong, C.c_int]),
     "dlv_diag_set": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "dlv_diag_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.c_int, C.c_int, C.POINTER(LayerPlan)]),
     "dlv_cells_csv": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dlv_reserve_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
     "dlv_debug_stamps": (C.c_int, [_P, _P]),

@@ -158,33 +158,12 @@ static int prof_drain(dlv_ctx* ctx) {
 }
 
 // ---- weight blob layout --------------------------------------------------------------------------
-static const int kConvLevel[DLV_N_CONV] = {0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 0, 0};
-
-static void conv_channels(const int f[6], int cin[DLV_N_CONV], int cout[DLV_N_CONV], int dcin[DLV_N_DECONV],
-                          int dcout[DLV_N_DECONV]) {
-    // MONAI BasicUNet topology (features f[0..5]); upcat_1 keeps its channels (halves=False)
-    int ci[DLV_N_CONV] = {1, f[0], f[0], f[1], f[1], f[2], f[2], f[3], f[3], f[4],
-                          f[3] + f[4] / 2, f[3], f[2] + f[3] / 2, f[2], f[1] + f[2] / 2, f[1], f[0] + f[1], f[5]};
-    int co[DLV_N_CONV] = {f[0], f[0], f[1], f[1], f[2], f[2], f[3], f[3], f[4], f[4],
-                          f[3], f[3], f[2], f[2], f[1], f[1], f[5], f[5]};
-    for (int i = 0; i < DLV_N_CONV; ++i) {
-        cin[i] = ci[i];
-        cout[i] = co[i];
-    }
-    int di[DLV_N_DECONV] = {f[4], f[3], f[2], f[1]};
-    int dco[DLV_N_DECONV] = {f[4] / 2, f[3] / 2, f[2] / 2, f[1]};
-    for (int j = 0; j < DLV_N_DECONV; ++j) {
-        dcin[j] = di[j];
-        dcout[j] = dco[j];
-    }
-}
-
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // walks the blob layout; if base != nullptr assigns the pointers into ctx
 static size_t layout_blob(dlv_ctx* ctx, const int f[6], char* base) {
     int cin[DLV_N_CONV], cout[DLV_N_CONV], dcin[DLV_N_DECONV], dcout[DLV_N_DECONV];
-    conv_channels(f, cin, cout, dcin, dcout);
+    dlv_unet_channels(f, cin, cout, dcin, dcout);
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? base + off : nullptr;
@@ -204,7 +183,7 @@ static size_t layout_blob(dlv_ctx* ctx, const int f[6], char* base) {
         uint16_t* wb16 = i == 0 ? nullptr : (uint16_t*)take(nw * 2);
         uint16_t* wh16 = i == 0 ? nullptr : (uint16_t*)take(nw * 2);
         // conv 16 = upcat_1.conv_0 when its inputs are a 32-channel skip + the 32 channels of a 32->32 transposed conv
-        const int slices = (i == 16 && cin[i] == 64 && cout[i] == 32 && dcin[3] == 32 && dcout[3] == 32) ? 1 : 0;
+        const int slices = dlv_conv_has_fold_pack(i, cin[i], cout[i], dcin[3], dcout[3]) ? 1 : 0;
         const bool fold = slices > 0;
         uint16_t* wsb = fold ? (uint16_t*)take((size_t)32 * 32 * 27 * 2) : nullptr;
         uint16_t* wsh = fold ? (uint16_t*)take((size_t)32 * 32 * 27 * 2) : nullptr;
@@ -237,8 +216,8 @@ static size_t layout_blob(dlv_ctx* ctx, const int f[6], char* base) {
         float* b = (float*)take((size_t)dcout[j] * 4);
         uint16_t* wb = (uint16_t*)take(nw * 2);
         uint16_t* wh = (uint16_t*)take(nw * 2);
-        uint16_t* wb16 = dcin[j] >= 128 ? (uint16_t*)take(nw * 2) : nullptr;
-        uint16_t* wh16 = dcin[j] >= 128 ? (uint16_t*)take(nw * 2) : nullptr;
+        uint16_t* wb16 = dlv_deconv_has_w16_pack(dcin[j]) ? (uint16_t*)take(nw * 2) : nullptr;
+        uint16_t* wh16 = dlv_deconv_has_w16_pack(dcin[j]) ? (uint16_t*)take(nw * 2) : nullptr;
         if (base) {
             ctx->deconv[j].w16_bf16 = wb16;
             ctx->deconv[j].w16_f16 = wh16;
@@ -300,7 +279,7 @@ int dlv_ctx_create(int device_id, void* stream, dlv_ctx** out) {
     if (!ctx) return DLV_ENOMEM;
     ctx->device = device_id;
 #ifdef DLV_DIAG  // the product library takes no kernel variant from the environment (diagnostic builds: make diag)
-    if (const char* e = getenv("DLV_ZM_VARIANT")) ctx->zm_variant = atoi(e);
+    if (const char* e = getenv("DLV_ZM_VARIANT")) ctx->sw.zm_variant = atoi(e);
 #endif
 #ifdef DLV_DIAG  // timing-only ablations (WRONG results): the diagnostic library only (make diag), never the product
     ctx->upconv_dbg = getenv("DLV_UPCONV_DBG") ? atoi(getenv("DLV_UPCONV_DBG")) : 0;
@@ -615,7 +594,7 @@ int dlv_unet_forward_dev(dlv_ctx* ctx, const float* x_dev, float* logits_dev, in
     if (!ctx || !x_dev || !logits_dev) return DLV_EINVAL;
     if (!ctx->weights_loaded) return dlv_fail(ctx, DLV_ESTATE, "dlv_unet_forward_dev before dlv_unet_load");
     if (B <= 0 || d <= 0 || h <= 0 || w <= 0) return dlv_fail(ctx, DLV_EINVAL, "empty batch/patch");
-    if (d < 16 || h < 16 || w < 16 || (long long)(d >> 4) * (h >> 4) * (w >> 4) < 2)
+    if (!dlv_window_supported(d, h, w))
         return dlv_fail(ctx, DLV_EUNSUP, "patch %dx%dx%d: every dimension must be at least 16 and level 4 (each dimension / 16, rounded down) must hold more "
                         "than one voxel - InstanceNorm3d has no statistics of a single value and torch raises there; any size from there on: "
                         "levels with an odd size are pooled and padded like MONAI's MaxPool3d / UpCat", d, h, w);
@@ -676,17 +655,10 @@ int dlv_cells_csv(const uint32_t* voxel_counts, const double* centroids, uint64_
 int dlv_diag_set(dlv_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return DLV_EINVAL;
     const std::string n(name);
-    if (n == "no_zmarch") ctx->no_zmarch = value != 0;
-    else if (n == "no_upconv") ctx->fold_up = value ? 0 : 1;
-    else if (n == "upconv_simple") ctx->upconv_simple = value ? 1 : 0;
-    else if (n == "fuse_levels") ctx->fuse_levels = value;
-    else if (n == "fuse_layers") ctx->fuse_layers = value;
-    else if (n == "zreg_mask") ctx->zreg_mask = value;
-    else if (n == "deep_mask") ctx->deep_mask = value;
-    else if (n == "generic_ncb") ctx->generic_ncb = value;
+    if (n == "zm_variant") return dlv_debug_set_zm_variant(ctx, value);  // (the product library refuses the diagnostic builds)
+    if (dlv_plan_switch_set(ctx->sw, name, value)) return DLV_OK;        // the switches that choose a layer's kernel (layer_plan.h)
+    if (n == "upconv_simple") ctx->upconv_simple = value ? 1 : 0;
     else if (n == "zreg_dbg") ctx->zreg_dbg = value;
-    else if (n == "deep_small") ctx->deep_small = value;
-    else if (n == "pool_rows_off") ctx->pool_rows_off = value != 0;
     else if (n == "erode_xy_split") ctx->erode_xy_split = value != 0;
     else if (n == "erode_z_two_sweeps") ctx->erode_z_two_sweeps = value != 0;
     else if (n == "ccl_simple") ctx->ccl_simple = value != 0;
@@ -705,8 +677,23 @@ int dlv_debug_set_zm_variant(dlv_ctx* ctx, int variant) {
     if (variant != 0 && variant != 50 && variant != 51)
         return dlv_fail(ctx, DLV_EUNSUP, "z-march variant %d is a diagnostic build: load libdelivr_hip_diag.so (make -C delivr_cfos_amd/csrc diag)", variant);
 #endif
-    ctx->zm_variant = variant;
+    ctx->sw.zm_variant = variant;
     return DLV_OK;
+}
+
+// the plan of one forward of a sliding-window pass, on the host alone (layer_plan.h)
+int dlv_diag_plan(const int features[6], const char* const* names, const int* values, int n, int fmt16, int B, int d, int h, int w,
+                  dlv_layer_plan* out) {
+    if (!features || !out || n < 0 || (n > 0 && (!names || !values)) || fmt16 < 0 || fmt16 > 2) return DLV_EINVAL;
+    DlvPlanSwitches sw;
+    bool upconv_simple = false;
+    for (int i = 0; i < n; ++i) {
+        if (!names[i]) return DLV_EINVAL;
+        if (strcmp(names[i], "upconv_simple") == 0) upconv_simple = values[i] != 0;  // (no kernel family: the upconv label's "m")
+        else if (strcmp(names[i], "zreg_dbg") == 0) continue;  // (another code path of the same kernel)
+        else if (!dlv_plan_switch_set(sw, names[i], values[i])) return DLV_EINVAL;
+    }
+    return dlv_plan_forward(sw, upconv_simple, features, fmt16, B, d, h, w, out) ? DLV_OK : DLV_EUNSUP;
 }
 
 int dlv_debug_stamps(dlv_ctx* ctx, void* buf_dev) {

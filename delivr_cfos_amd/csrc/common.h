@@ -13,6 +13,7 @@
 
 #include "../../include/delivr_hip.h"
 #include "../../include/delivr_hip_diag.h"  // (the layer test hook's report bits)
+#include "layer_plan.h"  // which kernel runs which layer: the switches, the predicates and dlv_cdiv
 
 #define DLV_WAVE 64
 #define DLV_MAX_LANES 6
@@ -97,8 +98,6 @@ struct dlv_ctx {
     float* blend_wsum = nullptr;
     int upconv_dbg = 0;         // DLV_UPCONV_DBG, diagnostic library only (timing, WRONG results): 1 = no stores, 2 = no halo loads
     int upconv_simple = 0;      // dlv_diag_set "upconv_simple": the one-tile-per-workgroup upconv kernel for every shape (A/B, tests)
-    int fold_up = 1;            // fold the transposed conv into the first conv of upcat_1 (upconv.hip); dlv_diag_set "no_upconv": the unfolded path
-    int zm_variant = 0;         // kernel variant of the z-march conv (0 = default; others: A/B and diagnostic builds)
     void* stamp_buf = nullptr;  // dlv_debug_stamps: timeline buffer of the diagnostic z-march build (DLV_ZM_VARIANT=30)
     int* range_flag = nullptr;  // device words: [0] 0, or 100 - (first layer whose InstanceNorm sums were not finite; 18 = logits);
                                 // [1 + layer] float bits of the largest |mean| + 8 sigma of the layer's raw output that exceeded 4096
@@ -119,26 +118,15 @@ struct dlv_ctx {
     size_t ws_bytes[WS_N_SLOTS] = {0};
     // timing
     bool debug_f16 = false;  // format used by dlv_debug_layer_bf16
-    bool no_zmarch = false;  // test switch: force the generic conv kernel
-    // Kernel-selection switches of tests and A/B runs (same results, other kernels).  The library takes NONE of them from the
-    // environment (a stray DLV_* in a user's shell must not change kernels): dlv_diag_set (include/delivr_hip_diag.h) sets them
-    // per context.  What the library does read from the environment: DLV_LANES, DLV_LAUNCH_LOG, DLV_RCCL_PATH / ROCM_PATH /
-    // DLV_FORCE_RCCL (transport), nothing else.
-    // bit li: conv block li applies the InstanceNorm + Mish of its first input itself while it stages the planes (no normalisation
-    // pass over that tensor).  Default: block 17 (upcat_1.conv_1) only - the one site where it pays: -1.4...-1.7 % of a pass on every
-    // workload, masks identical; block 16 (the raw skip tensor into the addend conv) +2.2 %, the level-1 sites +0.3...+0.9 %
-    // (profiles/r06z_fuse_sites_ab.txt).  The level-wise switch of rounds 2-6 saw the two level-0 sites cancel.
-    int fuse_layers = 1 << 17;
-    int fuse_levels = 0;     // bit l: raw tensors of level l are activated by the z-reg conv that stages them (no norm pass)
-    int zreg_mask = 3;       // 1 = Cin 32, 2 = Cin 64 layers may take the register-resident-weights conv
-    int deep_mask = 2;       // conv_deep.hip: bit 0 = the layers the LDS-weights z-march also takes, bit 1 = the others
-    int generic_ncb = 0;     // cout blocks per workgroup of the generic conv (0: its own choice)
+    // Kernel-selection switches of tests and A/B runs that decide which kernel runs a layer (layer_plan.h; dlv_diag_set sets them
+    // per context).  The library takes no switch from the environment; what it does read there: DLV_LANES, DLV_LAUNCH_LOG,
+    // DLV_RCCL_PATH / ROCM_PATH / DLV_FORCE_RCCL (transport), nothing else.
+    DlvPlanSwitches sw;
     int zreg_dbg = 0;        // 1 = edge-step code on every plane of the z-reg conv
     // what the last launches ran, for the layer test hook (dlv_debug_layer16): z-reg instantiation (DLV_DBG_ZR_* bits, 0 = none)
     // and upconv kernel (1 = one tile per workgroup, 2 = persistent, 0 = none)
     int ran_zreg = 0, ran_upconv = 0;
-    int deep_small = 1;      // 0 = levels smaller than a tile of conv_deep.hip and its 32-output-channel layers take the generic conv (A/B)
-    bool pool_rows_off = false, erode_xy_split = false, erode_z_two_sweeps = false, ccl_simple = false;
+    bool erode_xy_split = false, erode_z_two_sweeps = false, ccl_simple = false;
     bool resample_simple = false, resample_run16 = false;
     int tiff_chunk = 0;      // planes per staging chunk of dlv_tiff_stack_to_device (0: ~256 MB; tests: the double-buffer hand-over on small planes)
     bool prof_on = false;
@@ -186,8 +174,6 @@ struct DlvProf {
     ~DlvProf();
     void end();
 };
-
-static inline int dlv_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // "this kernel's dynamic-LDS attribute is set on this device": one bit per device in a function-local static.  The ranks of
 // dlv_sw_infer_sharded are host threads that go through the same launchers, so the bits are atomic (a lost race only
@@ -249,11 +235,9 @@ int dlv_conv3_zmarch_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const voi
                             const void* wpk, const float* bias, void* out, float* partials, int B, int D, int H, int W,
                             int* nparts);
 // deep-level conv (conv_deep.hip): LDS-shared weights, persistent workgroups; wpk16 = the 16-channel A-fragment pack
-bool dlv_conv3_deep_supports(int cin, int cout, int c1, int c2, int D, int H, int W);
 int dlv_conv3_deep_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const void* in1, int c1, const void* in2, int c2, const void* wpk16,
                           void* out, float* partials, int B, int D, int H, int W, int* nparts);
 // transposed conv of the deep levels (conv_deep.hip): Cin 128 / 256, LDS-shared weights; `in` holds final (activated) values
-bool dlv_deconv2_deep_supports(int cin, int cout, int D, int H, int W);
 int dlv_pack_deconv_w16(dlv_ctx* ctx, bool f16, const float* w_f32, uint16_t* out, int cin, int cout);
 int dlv_deconv2_deep_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const void* in, const void* wpk16, const float* bias, void* out, int B,
                             int D, int H, int W);
@@ -270,7 +254,6 @@ int dlv_pack_upconv(dlv_ctx* ctx, bool f16, const float* wc, int ctot, int cs, c
 bool dlv_upconv2_persistent(const dlv_ctx* ctx, int Dc, int Hc, int Wc);
 int dlv_upconv2_launch(dlv_ctx* ctx, bool f16, const void* in, const void* wpk, const float* corr, void* out, int B, int Dc, int Hc, int Wc,
                        int cstride = 4, int c0 = 0);
-bool dlv_conv3_zreg_supports(int cin, int cout, int c1, int c2, int W);
 // range guard of the 16-bit formats (unet_bf16.hip): reset before a pass / forward, check after it (synchronises the stream)
 int dlv_range_reset(dlv_ctx* ctx);
 int dlv_range_check(dlv_ctx* ctx, int fmt16);

@@ -558,11 +558,6 @@ int dd_launch(dlv_ctx* ctx, const void* in, const void* wpk16, const float* bias
 // 4 x 4 x 2 of run_inference's own (64, 64, 32), inference/inference.py:119) run as partly filled tiles - out-of-window lanes
 // read zeros and store nothing: still 3-4x the generic kernel, whose waves each pull their own weight fragments from L2 - and
 // so do the 32-output-channel layers of a level whose rows are shorter than the 32 voxels the z-reg / z-march tiles need
-bool dlv_conv3_deep_supports(int cin, int cout, int c1, int c2, int D, int H, int W) {
-    return cin % 32 == 0 && c1 % 32 == 0 && c2 % 32 == 0 && c1 + c2 == cin && cout % 32 == 0 && cout >= 32 && W >= 2 && H >= 2 && D >= 2 &&
-           (long long)D * H * W <= 32768;
-}
-
 // raw conv output + InstanceNorm partial sums partials[((n * nparts + part) * cout + co) * 2 + {sum, sum of squares}]
 int dlv_conv3_deep_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const void* in1, int c1, const void* in2, int c2, const void* wpk16,
                           void* out, float* partials, int B, int D, int H, int W, int* nparts) {
@@ -592,9 +587,6 @@ int dlv_conv3_deep_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const void*
 }
 
 // ---- transposed conv of the deep levels -------------------------------------------------------------------------------------
-bool dlv_deconv2_deep_supports(int cin, int cout, int D, int H, int W) {
-    return (cin == 128 || cin == 256) && cout % 64 == 0 && cout > 0 && (long long)D * H * W <= 32768 && W >= 1;
-}
 int dlv_pack_deconv_w16(dlv_ctx* ctx, bool f16, const float* w_f32, uint16_t* out, int cin, int cout) {
     if (f16) hipLaunchKernelGGL(pack_deconv_w16_kernel<PF16>, dim3(64), dim3(256), 0, ctx->stream, w_f32, out, cin, cout);
     else hipLaunchKernelGGL(pack_deconv_w16_kernel<PBf16>, dim3(64), dim3(256), 0, ctx->stream, w_f32, out, cin, cout);

@@ -913,7 +913,7 @@ int dlv_conv3_zmarch_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const voi
                             int* nparts) {
     if (cout % 32 || cout <= 0) return dlv_fail(ctx, DLV_EUNSUP, "z-march conv: Cout must be a multiple of 32");
     const int ncb = cout / 32;
-    const int variant = ctx->zm_variant;  // DLV_ZM_VARIANT at context creation, or dlv_debug_set_zm_variant
+    const int variant = ctx->sw.zm_variant;  // DLV_ZM_VARIANT at context creation, or dlv_debug_set_zm_variant
     // 16-row tiles (8 waves x 2 rows) only as A/B variant 3: measured equal/slower than 8 rows x 1 (profiles/README.md)
 #ifdef DLV_DIAG
     const int tyt = (cin == 32 && variant == 3) ? 16 : 8;

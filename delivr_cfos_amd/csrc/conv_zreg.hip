@@ -44,11 +44,6 @@ int dlv_pack_conv_w16(dlv_ctx* ctx, bool f16, const float* w_f32, uint16_t* out,
     return DLV_OK;
 }
 
-bool dlv_conv3_zreg_supports(int cin, int cout, int c1, int c2, int W) {
-    return cout % 32 == 0 && cout > 0 && W >= 32 &&
-           ((cin == 32 && c1 == 32 && c2 == 0) || (cin == 64 && ((c1 == 32 && c2 == 32) || (c1 == 64 && c2 == 0))));
-}
-
 // the register-resident-weights conv.  ss1 / ss2: InstanceNorm scale/shift [n][C] of the layer that produced in1 / in2
 // (applied with Mish while staging), or nullptr for an input that is already final (stem output, pooled tensor, deconv
 // output).  Returns the number of partial-sum rows per sample in *nparts.
@@ -63,11 +58,7 @@ int dlv_conv3_zreg_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const void*
     if ((long long)D * H * W >= (1ll << 26)) return dlv_fail(ctx, DLV_EUNSUP, "z-reg conv: window too large for 32-bit plane offsets (buffer resources of 2 x 16 B x voxels)");
     const int ncb = cout / 32;
     const bool act = ss1 != nullptr || ss2 != nullptr;
-    // tile height: 16 rows (Cin = 32 only) for windows large enough that 16 of them fill the chip with z-columns of at
-    // least 64 planes.  The choice depends on the window shape only, never on the batch size: the InstanceNorm partial
-    // sums are per tile, so a window's result must not depend on how many windows share its launch
-    int tyt = 8;
-    if (cin == 32 && H % 16 == 0 && (long long)(H / 16) * dlv_cdiv(W, 32) * ncb * dlv_cdiv(D, 64) >= 16) tyt = 16;
+    int tyt = dlv_conv3_zreg_tile_rows(cin, cout, D, H, W);  // (layer_plan.h: a property of the window shape, never of the batch)
 #ifdef DLV_DIAG  // A/B switches of the diagnostic library (profiles/tools/tyt_ab.sh, minwg_ab.sh)
     static const int force_tyt = getenv("DLV_ZREG_TYT") ? atoi(getenv("DLV_ZREG_TYT")) : 0;
     if (force_tyt == 8 || (force_tyt == 16 && cin == 32)) tyt = force_tyt;

@@ -395,7 +395,7 @@ int dlv_sw_infer_dev(dlv_ctx* ctx, const dlv_sw_params* p, const uint16_t* vol_d
     Tiler t;
     DLV_TRY(build_tiler(ctx, p, t));
     const int d = t.roi[0], h = t.roi[1], w = t.roi[2];
-    if (d < 16 || h < 16 || w < 16 || (long long)(d >> 4) * (h >> 4) * (w >> 4) < 2)
+    if (!dlv_window_supported(d, h, w))
         return dlv_fail(ctx, DLV_EUNSUP, "window %dx%dx%d: every dimension must be at least 16 and level 4 (each dimension / 16, rounded down) must hold more "
                         "than one voxel - InstanceNorm3d has no statistics of a single value and torch raises there; any size from there on: "
                         "levels with an odd size are pooled and padded like MONAI's MaxPool3d / UpCat", d, h, w);

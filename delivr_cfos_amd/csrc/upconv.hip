@@ -459,9 +459,8 @@ int dlv_pack_upconv(dlv_ctx* ctx, bool f16, const float* wc, int ctot, int cs, c
 
 // does the persistent kernel take this shape?  Full tiles only; 24-bit halo offsets, 31-bit offsets within a wave's two output chunks
 bool dlv_upconv2_persistent(const dlv_ctx* ctx, int Dc, int Hc, int Wc) {
-    const long long voxc = (long long)Dc * Hc * Wc;
-    return !ctx->upconv_simple && Dc > 0 && Dc % UC_TZ == 0 && Hc % UC_TY == 0 && Wc % UC_TX == 0 &&
-           ((long long)(UC_HZ - 1) * Hc + UC_HY) * Wc * 16 < (1 << 24) && voxc * 8 * 16 * 2 < (1LL << 31);
+    static_assert(UC_TZ == 4 && UC_TY == 8 && UC_TX == 16, "dlv_upconv2_persistent_shape (layer_plan.h) is written for these tiles");
+    return !ctx->upconv_simple && dlv_upconv2_persistent_shape(Dc, Hc, Wc);
 }
 
 // in: activated coarse tensor (B, 8 * cstride ch, Dc, Hc, Wc) chunk-planar, of which the four chunks from c0 are this launch's 32

@@ -160,6 +160,32 @@ def shared_engine(device: int = 0) -> "HipEngine":
     return eng
 
 
+def layer_plan(window, switches=None, precision="fp16", batch=1, features=(32, 32, 64, 128, 256, 32)):
+    """Which kernel runs each layer of one forward of a sliding-window pass over `window` = (d, h, w), under the dlv_diag_set
+    `switches` {name: value} - dlv_diag_plan: what the forward itself consults (csrc/layer_plan.h), computed on the host; needs
+    no GPU and no engine.  Returns {"conv": 18 dicts, "deconv": 4, "pool": 4, "labels": [(label, flops, bytes)] in launch order};
+    kernels by name (_lib.PLAN_CONV_KERNELS / PLAN_DECONV_KERNELS), None = not launched."""
+    lib = _lib.load()
+    sw = dict(switches or {})
+    names = (C.c_char_p * max(1, len(sw)))(*[k.encode() for k in sw])
+    values = (C.c_int * max(1, len(sw)))(*[int(v) for v in sw.values()])
+    out = _lib.LayerPlan()
+    rc = lib.dlv_diag_plan((C.c_int * 6)(*features), names, values, len(sw), {"bf16_all": 0, "fp16": 1, "bf16": 2}[precision], int(batch),
+                           *(int(v) for v in window), C.byref(out))
+    if rc != 0:
+        raise DelivrHipError(rc, f"dlv_diag_plan: window {tuple(window)}, switches {sw}")
+
+    def fields(st, kernels):
+        d = {name: getattr(st, name) for name, _ in st._fields_}
+        d["kernel"] = None if st.kernel < 0 else kernels[st.kernel]
+        return d
+
+    return {"conv": [fields(c, _lib.PLAN_CONV_KERNELS) for c in out.conv],
+            "deconv": [fields(c, _lib.PLAN_DECONV_KERNELS) for c in out.deconv],
+            "pool": [{name: getattr(p, name) for name, _ in p._fields_} for p in out.pool],
+            "labels": [(out.labels[i].value.decode(), out.flops[i], out.bytes[i]) for i in range(out.n_labels)]}
+
+
 class HipEngine:
     shared = False  # True: owned by shared_engine() - callers that "own" their engine must not close it
 

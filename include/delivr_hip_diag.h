@@ -88,6 +88,54 @@ typedef struct dlv_debug_layer_args {
 } dlv_debug_layer_args;
 int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args);
 
+/* Which kernel runs each layer of ONE 16-bit forward of a sliding-window pass (stem from the uint16 volume, final conv
+ * blending) of B windows of d x h x w, without running it: host arithmetic only (delivr_cfos_amd/csrc/layer_plan.h, what the
+ * forward itself consults) - no context, no HIP call, no GPU.  names / values: n switches as given to the switch setter above
+ * (plus "zm_variant"); fmt16: 0 = bf16 everywhere, 1 = fp16, 2 = fp16 at level 0 + bf16 below (DLV_PREC_BF16).
+ * DLV_EINVAL for an unknown switch, DLV_EUNSUP for features or a window the 16-bit forward refuses. */
+#define DLV_PLAN_NONE (-1)       /* not launched (deconv 3 when upcat_1 is folded) */
+#define DLV_PLAN_ZREG 0          /* conv_zreg_kernel.h: register-resident weights */
+#define DLV_PLAN_DEEP 1          /* conv_deep.hip */
+#define DLV_PLAN_ZMARCH 2        /* conv_zmarch.hip: LDS-resident weights */
+#define DLV_PLAN_GENERIC 3       /* conv3_mfma_kernel */
+#define DLV_PLAN_STEM_MFMA 4     /* conv[0] only */
+#define DLV_PLAN_STEM_VALU 5
+#define DLV_PLAN_DC_DEEP 0       /* transposed convs: conv_deep.hip, */
+#define DLV_PLAN_DC_REGW 1       /* register-resident weights, */
+#define DLV_PLAN_DC_WST 2        /* weight-stationary, */
+#define DLV_PLAN_DC_ROWS 3       /* row segments, */
+#define DLV_PLAN_DC_PARITY 4     /* one output parity per launch item */
+#define DLV_PLAN_MAX_LABELS 96
+typedef struct dlv_plan_conv {
+    int kernel, level, cin, cout; /* cin / cout of the launch: the folded block 16 runs its 32-channel skip half */
+    int folded;                   /* upconv + z-reg conv with addend */
+    int tile_rows;                /* ZREG: 8 / 16 */
+    int act_on_load;              /* the conv activates its raw first input while staging (no normalisation pass) */
+    int tx, ncb, wlds;            /* GENERIC: tile width, cout blocks per workgroup (the one field that follows B), weights through LDS */
+    long long max_parts;          /* bound on the InstanceNorm partial-sum rows per sample */
+} dlv_plan_conv;
+typedef struct dlv_plan_deconv {
+    int kernel;     /* DLV_PLAN_DC_*, DLV_PLAN_NONE */
+    int norm_first; /* a normalisation pass makes its input final first (else: activated on load) */
+    int padded;     /* followed by UpCat's replicate padding (odd skip tensor) */
+} dlv_plan_deconv;
+typedef struct dlv_plan_pool { /* the pass that pools level l into level l + 1 */
+    int rows;       /* the kernel that walks full lines (else one pooled voxel per thread) */
+    int writeback;  /* it also writes the activated level-l tensor back */
+    int norm_after; /* odd level: pool only, then a full normalisation pass */
+    int nt;         /* non-temporal policy (a tensor far beyond the caches: follows B, changes no value) */
+} dlv_plan_pool;
+typedef struct dlv_layer_plan {
+    dlv_plan_conv conv[DLV_N_CONV];
+    dlv_plan_deconv deconv[DLV_N_DECONV];
+    dlv_plan_pool pool[4];
+    int n_labels;                          /* kernel-timer labels in launch order, with their algorithmic FLOPs and bytes */
+    char labels[DLV_PLAN_MAX_LABELS][48];
+    double flops[DLV_PLAN_MAX_LABELS], bytes[DLV_PLAN_MAX_LABELS];
+} dlv_layer_plan;
+int dlv_diag_plan(const int features[6], const char* const* names, const int* values, int n, int fmt16, int B, int d, int h, int w,
+                  dlv_layer_plan* out);
+
 #ifdef __cplusplus
 }
 #endif

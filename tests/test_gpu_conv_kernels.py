@@ -158,10 +158,40 @@ def _reference(net, row, fmt, x1, ss, x2):
     return lr.conv_block(x1, blk.conv.weight.detach(), blk.conv.bias.detach(), N.weight.detach(), N.bias.detach(), fmt, ss1=ss, x2=x2)
 
 
-def _switches(eng, row):
+def _switch_values(row):
     # the activating instantiations run where the dispatcher lets block li activate its first input (fuse_layers bit li);
     # the default (bit 17 only) otherwise
-    eng.diag_set("fuse_layers", (1 << 17) | ((1 << row.li) if row.act else 0))
+    return {"fuse_layers": (1 << 17) | ((1 << row.li) if row.act else 0)}
+
+
+def _switches(eng, row):
+    for name, value in _switch_values(row).items():
+        eng.diag_set(name, value)
+
+
+_LEVEL = (0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 0, 0)
+
+
+def _planned(row, fmt, B):
+    """what the plan (csrc/layer_plan.h through dlv_diag_plan) says of block row.li on row.shape under the row's switches: the
+    z-reg instantiation and the upconv kernel in the words of the hook's report.  The plan is of a whole forward: the window
+    whose level of block li has the row's shape."""
+    from delivr_cfos_amd.engine import layer_plan
+
+    window = tuple(n << _LEVEL[row.li] for n in row.shape)
+    plan = layer_plan(window, _switch_values(row), precision="fp16" if fmt == "fp16" else "bf16_all", batch=B)
+    c = plan["conv"][row.li]
+    inst = None
+    if c["kernel"] == "ZREG":
+        # (the plan is of a forward, where the first input of block li is raw; a row that hands the hook a final tensor leaves the
+        # conv nothing to activate: plan_conv with raw1 = false)
+        act = bool(c["act_on_load"]) and row.act
+        assert bool(c["act_on_load"]) or not row.act, c
+        suffix = ("adda1" if act else "add") if c["folded"] else ("a1" if act else "a0")
+        inst = f"{'f16' if fmt == 'fp16' else 'bf16'}_c{c['cin']}_t{c['tile_rows']}_{suffix}"
+    upconv = [l.split("_")[0] for l, _, _ in plan["labels"] if l.startswith("upconv2")]
+    assert len(upconv) == (1 if plan["conv"][16]["folded"] else 0), plan["labels"]  # (a forward's one upconv launch belongs to block 16)
+    return inst, bool(c["folded"]), upconv[0] if c["folded"] else None
 
 
 def _run(eng, row, fmt, kind, x1, ss, x2):
@@ -188,11 +218,55 @@ def test_zreg_instantiation_vs_fp64(eng, net, row):
         eng.diag_set("fuse_layers", 1 << 17)
     assert rep["zreg"] == row.inst and rep3["zreg"] == row.inst, (rep, row.inst)
     assert rep["upconv"] == row.upconv, rep
+    # ... and it is what the plan says of this shape under these switches: instantiation (format, Cin, tile rows, activation
+    # on load, addend) and an upconv launch exactly where the plan folds
+    p_inst, p_folded, p_upconv = _planned(row, fmt, B)
+    assert p_inst == rep["zreg"], (p_inst, rep)
+    assert p_folded == (rep["upconv"] is not None) == (row.op == "folded"), (p_folded, rep)
+    assert p_upconv == rep["upconv"], (p_upconv, rep)
     tyt = 16 if "_t16_" in row.inst else 8
     what = f"{row.inst} {row.op} block {row.li} {row.shape}"
     mx = _check_final(out.cpu(), ref["out"], fmt, row.shape, tyt, what)
     se = _check_scale(ssg.cpu(), ref, rep3["raw_scale"], what)
     print(f"RESULT {what}: max {mx:.3e} scale {se:.3e}")
+
+
+# ---------------------------------------------------------------------------------------------------
+# a whole forward runs the launches its plan lists
+# ---------------------------------------------------------------------------------------------------
+# 16 x 48 x 64: 8-row z-reg tiles at level 0; 16 x 128 x 64: the smallest window with 16-row tiles; 24 x 40 x 72: odd levels
+# (12 x 20 x 36 -> 6 x 10 x 18 -> 3 x 5 x 9): replicate padding and the pool-then-normalise path
+@pytest.mark.parametrize("fmt", ["fp16", "bf16"])
+@pytest.mark.parametrize("window", [(16, 48, 64), (16, 128, 64), (24, 40, 72)], ids=lambda w: "x".join(map(str, w)))
+def test_forward_launches_the_labels_of_its_plan(eng, window, fmt):
+    import torch
+
+    from delivr_cfos_amd.engine import layer_plan
+
+    plan = layer_plan(window, {}, precision=fmt)
+    assert plan["conv"][1]["tile_rows"] == (16 if window == (16, 128, 64) else 8) and plan["conv"][1]["kernel"] == "ZREG"
+    assert any(q["norm_after"] for q in plan["pool"]) == (window == (24, 40, 72))
+    vol = torch.randint(1, 60000, window, generator=torch.Generator().manual_seed(2), dtype=torch.int32).to(torch.uint16).cuda()
+    acc = torch.zeros(window, dtype=torch.float32, device="cuda")
+    eng.prof_reset()
+    eng.prof_enable(True)
+    try:
+        eng.sw_infer(eng.make_sw_params(window, window, 0.5, None, 0, fmt), vol, acc)  # one window
+        eng.sync()
+        ran = eng.prof_report()
+    finally:
+        eng.prof_enable(False)
+        eng.prof_reset()
+    tiler = {"window_max_u16", "skip_fill_f32"}  # (sw_infer.hip's own launches around the forward)
+    planned = {l for l, _, _ in plan["labels"]}
+    assert set(ran) - tiler == planned, (sorted(set(ran) - tiler - planned), sorted(planned - set(ran)))
+    # one pass of one window: as many launches under each label as the plan lists, with its algorithmic FLOPs and bytes
+    for label in planned:
+        n = sum(1 for l, _, _ in plan["labels"] if l == label)
+        assert ran[label]["launches"] == n, (label, ran[label], n)
+        assert ran[label]["flops"] == sum(f for l, f, _ in plan["labels"] if l == label), label
+        assert ran[label]["bytes"] == sum(b for l, _, b in plan["labels"] if l == label), label
+    assert bool(torch.isfinite(acc).all())
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -14,7 +14,10 @@ import pickle
 import numpy as np
 
 from . import hostio
-from .hostlogic import cells_csv_bytes, csv_name, size_filter_bounds
+from .hostlogic import (INTENSITY_KEYS, cell_intensity_csv_text, cells_csv_bytes, csv_name, finish_intensity, intensity_stats_enabled,
+                        merge_intensity, size_filter_bounds)
+
+_INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
 
 
 def _find_cached(path: str, suffix: str, brain: str):
@@ -78,13 +81,54 @@ def _note_filter(bounds, n_before: int, n_kept: int, voxels_removed: int, quiet:
               f"removed {voxels_removed} voxels")
 
 
-def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None):
+def _open_raw_volume(settings, brain, shape):
+    """The raw volume of settings["mi355x"]["intensity_stats"]: the first *.npy (sorted) under <blob_detection input>/<brain>/
+    masked_niftis - the file run_inference reads - as a read-only memmap without its leading singleton axes -> (memmap, path).
+    FileNotFoundError without the folder or a file in it; ValueError unless it is a C-ordered uint16 volume at least as large as
+    the stack on every axis (the file is padded to window multiples)."""
+    nifti_dir = os.path.join(settings["blob_detection"]["input_location"], brain, "masked_niftis")
+    files = sorted(f for f in os.listdir(nifti_dir) if f.endswith(".npy"))
+    if not files:
+        raise FileNotFoundError(f"count_blobs: settings['mi355x']['intensity_stats'] needs the raw volume, no .npy file in {nifti_dir}")
+    path = os.path.join(nifti_dir, files[0])
+    vol = np.load(path, mmap_mode="r")
+    while vol.ndim > 3 and vol.shape[0] == 1:
+        vol = vol[0]
+    if vol.dtype != np.uint16 or vol.ndim != 3 or not vol.flags.c_contiguous or any(r < v for r, v in zip(vol.shape, shape)):
+        raise ValueError(f"count_blobs: the raw volume {path} ({vol.dtype}, shape {tuple(vol.shape)}) is not a C-ordered uint16 volume "
+                         f"that holds the stack of shape {tuple(shape)}")
+    return vol, path
+
+
+def _intensity_of(eng, labels_dev, raw_planes, N):
+    """raw_planes: the planes of the raw memmap that lie under labels_dev (whole planes: the Y / X padding stays, the pitches
+    describe it) -> HipEngine.cc_intensity's dict; the raw tensor is gone when this returns"""
+    raw_dev = hostio.upload(eng, raw_planes, what="h2d_raw")
+    try:
+        return eng.cc_intensity(labels_dev, raw_dev, N)
+    finally:
+        del raw_dev
+
+
+def _write_intensity_table(path_out, brain, stats, N, raw_file):
+    """<output_location>/cell_intensity/<brain>.csv - in a sub-folder, so that no cache look-up (_find_cached: any entry with
+    '.npy' / '.pickle' and the brain's name) and no reader of the reference's CSV ever matches it"""
+    folder = os.path.join(path_out, "cell_intensity")
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
+        fh.write(cell_intensity_csv_text(stats, N))
+    count_blobs.last_intensity = {"n": int(N), "raw_file": raw_file}
+
+
+def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_vol=None):
     """One process per GPU: every rank labels a Z-slab of the mask, seams are merged (parallel.ccl_sharded) and every
     rank writes ITS label slab straight into the output .npy (rank 0 creates the file once N - and with it the label
     dtype - is known); only the merged statistics travel to rank 0.  No rank ever holds the whole label volume (17 GB for
     1024x2048x2048).  bounds: the size filter (hostlogic.size_filter_bounds) - every rank counts the voxels of the global
     labels in its slab, the counts are summed over the ranks, every rank applies the same filter to its slab and the
-    statistics are taken on the filtered labels.  Returns (N, stats | None)."""
+    statistics are taken on the filtered labels.  raw_vol: the raw volume (settings["mi355x"]["intensity_stats"]) - every
+    rank measures planes [lo, hi) of it under its final global labels, rank 0 merges the parts into its stats.
+    Returns (N, stats | None)."""
     from .parallel import ccl_sharded, merge_stats
 
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -131,6 +175,24 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None):
         stats = None
         if rank == 0:  # (the labels are global and final already: identity tables)
             stats = merge_stats([np.arange(N + 1, dtype=np.uint32)] * world, raws, [s[0] for s in slabs], (Z, Y, X), N)
+    if raw_vol is not None:
+        # (as for the filter: the outcome of every rank's pass, and then of rank 0's merge, is exchanged before the next collective)
+        part, failed = None, None
+        try:
+            if labels is not None:
+                part = _intensity_of(eng, labels, raw_vol[lo:hi], N)
+        except Exception as exc:
+            failed = f"rank {rank}: {exc!r}"
+        _raise_if_any_failed(dist, failed, "count_blobs: the intensity statistics")
+        parts = [None] * world
+        dist.gather_object(part, parts if rank == 0 else None, dst=0)
+        failed = None
+        if rank == 0:
+            try:
+                stats.update(finish_intensity(merge_intensity(parts), stats["voxel_counts"]))
+            except Exception as exc:
+                failed = f"rank 0: {exc!r}"
+        _raise_if_any_failed(dist, failed, "count_blobs: merging the intensity statistics")
     out_path = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
     err = [None]
     if rank == 0:
@@ -181,11 +243,20 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     renumbered 1..K in the order they had and everything written - label file, its name and dtype, statistics, CSV - is what
     the mask without the removed components would have given; ``count_blobs.last_filter`` holds the numbers.  A cached label
     file is reused as it is: the bounds are NOT re-applied to it.  A mask that needs the slab-streamed path (larger than the
-    HBM budget) is refused with the filter on."""
+    HBM budget) is refused with the filter on.
+
+    ``settings["mi355x"]["intensity_stats"]`` true: the raw volume run_inference read (the first .npy under
+    <blob_detection input_location>/<brain>/masked_niftis) is measured under the final labels on the device - per label the
+    sum, the sum of squares, the minimum and the maximum of the raw intensities, exact integers, and their mean.  The five arrays
+    become keys of <brain>-stats.pickle (intensity_sum / _sumsq / _min / _max / _mean, N+1 rows, row 0 zero), the table goes to
+    <output_location>/cell_intensity/<brain>.csv and ``count_blobs.last_intensity`` holds {"n", "raw_file"}.  Cached labels are
+    measured too, and a cached pickle without the keys is rewritten with them.  A missing or too small raw volume is an error
+    before any file is written; a mask that needs the slab-streamed path is refused.  Off or absent: nothing of this happens."""
     from .engine import shared_engine
 
     bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
     count_blobs.last_filter = None  # set by a run that filtered
+    count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     if bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
         print(f"min_size {min_size} / max_size {max_size} are ignored, as in the reference; "
               "settings['mi355x']['size_filter'] = true applies them")
@@ -197,13 +268,24 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         dist, sharded = None, False
     rank = dist.get_rank() if sharded else 0
 
+    shape = tuple(int(v) for v in stack_shape[2:])
+    raw_vol, raw_file = None, None
+    if intensity_stats_enabled(settings):  # (before any file is written; under torch.distributed all ranks raise or none does)
+        failed = None
+        try:
+            raw_vol, raw_file = _open_raw_volume(settings, brain, shape)
+        except (OSError, ValueError) as exc:
+            if not sharded:
+                raise
+            failed = f"rank {rank}: {exc!r}"
+        if sharded:
+            _raise_if_any_failed(dist, failed, "count_blobs: opening the raw volume of the intensity statistics")
     path_out = settings["postprocessing"]["output_location"]
     os.makedirs(path_out, exist_ok=True)  # (every rank may get here first)
     len_b = len(os.listdir(path_in))
     start = datetime.datetime.now()
     print(f"{start} Now postprocessing inference for {brain} - {brain_i}/{len_b}")
     brain_path = os.path.join(path_in, brain, "binary_segmentations", "binaries.npy")
-    shape = tuple(int(v) for v in stack_shape[2:])
     bin_img = np.memmap(brain_path, dtype=np.uint8, mode="r", shape=shape, offset=128)
     own = False  # (the shared engine outlives the call)
     eng = engine or shared_engine(int(os.environ.get("LOCAL_RANK", 0)) if sharded else 0)
@@ -221,7 +303,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
             raise RuntimeError(f"count_blobs: rank 0 failed while looking for a cached labelling: {branch[0][1]}")
         if not branch[0][1]:
             try:
-                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds)
+                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds, raw_vol)
             finally:
                 if own:
                     eng.close()
@@ -232,6 +314,8 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
                         pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
                     with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
                         fh.write(cells_csv_bytes(stats, N))
+                    if raw_vol is not None:
+                        _write_intensity_table(path_out, brain, stats, N, raw_file)
                     end = datetime.datetime.now()
                     print(f"{end} {brain} {brain_i} / {len_b} Done ({dist.get_world_size()} ranks); Took {end - start}")
                 except Exception as exc:
@@ -252,10 +336,12 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     try:
         import time
 
-        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds)
+        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
+        if raw_vol is not None:
+            _write_intensity_table(path_out, brain, stats, N, raw_file)
         count_blobs.last_timings["csv_s"] = time.perf_counter() - t_csv
         t_join = time.perf_counter()
         if defer_write:
@@ -275,11 +361,12 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None):
+def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
     made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
-    filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write."""
+    filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write.  raw_vol: the
+    raw volume (settings["mi355x"]["intensity_stats"]), measured under the labels - fresh or cached - after cc_stats."""
     import time
 
     labels_dev = None
@@ -297,6 +384,13 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
 
         budget = hbm_budget_bytes(eng, settings)
         need = int(bin_img.size) * ccl_bytes_per_voxel()
+        Z = int(bin_img.shape[0])
+        if raw_vol is not None and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 2) > budget:
+            # (the planes of the raw volume sit in HBM beside the labels: 2 more bytes per voxel - and no slab-streamed measuring)
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_stats'] needs the mask, its labels and the raw "
+                              f"volume in HBM ({int(bin_img.size) * (ccl_bytes_per_voxel() + 2) / 2**30:.1f} GiB), the HBM budget is "
+                              f"{budget / 2**30:.1f} GiB and the slab-streamed labelling does not measure; raise "
+                              "settings['mi355x']['hbm_budget_gb'] or switch intensity_stats off")
         if not cached and need > budget:
             # the mask + its uint32 labels do not fit this GPU: Z-slabs through the device, seams merged on the host
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
@@ -370,6 +464,31 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
         mid = datetime.datetime.now()
         print(f"{mid} labelling+writing/loading took {mid - start} : {N}")
         cached_stats = load_cached_stats(settings, brain)
+
+        def cached_labels_to_device():
+            import torch
+
+            if labels.dtype == np.uint32:
+                return hostio.upload(eng, labels, what="h2d_labels")
+            if labels.dtype == np.uint16:  # widened in HBM, not on the host
+                return hostio.upload(eng, labels, what="h2d_labels").view(torch.int16).to(torch.int32) & 0xFFFF
+            return torch.from_numpy(np.ascontiguousarray(labels).astype(np.uint32).view(np.int32)).to(eng.device)
+
+        def write_stats(path):
+            with open(path, "wb") as fh:
+                pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
+
+        have_intensity = False
+        if cached_stats:
+            print(f"Found stats at {cached_stats}")
+            with open(cached_stats, "rb") as fh:
+                stats = pickle.load(fh)
+            have_intensity = all(k in stats for k in _INTENSITY_STATS_KEYS)
+        measure = raw_vol is not None and not have_intensity
+        if measure and labels_dev is None and int(labels.size) * (4 + 2) > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_stats'] needs the cached labels and the raw volume "
+                              f"in HBM ({int(labels.size) * 6 / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
+                              "settings['mi355x']['hbm_budget_gb'] or switch intensity_stats off")
         if not cached_stats:
             if labels_dev is None and int(labels.size) * 4 > budget:
                 # cached labels that do not fit the HBM budget: statistics slab by slab (raw sums add up; streaming.py)
@@ -378,22 +497,18 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                 stats = stats_streamed(eng, labels, N, budget)
             else:
                 if labels_dev is None:
-                    import torch
-
-                    if labels.dtype == np.uint32:
-                        labels_dev = hostio.upload(eng, labels, what="h2d_labels")
-                    elif labels.dtype == np.uint16:  # widened in HBM, not on the host
-                        labels_dev = hostio.upload(eng, labels, what="h2d_labels").view(torch.int16).to(torch.int32) & 0xFFFF
-                    else:
-                        labels_dev = torch.from_numpy(np.ascontiguousarray(labels).astype(np.uint32).view(np.int32)).to(eng.device)
+                    labels_dev = cached_labels_to_device()
                 stats = eng.cc_stats(labels_dev, N)
-            with open(os.path.join(path_out, f"{brain}-stats.pickle"), "wb") as fh:
-                pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
+            if not measure:
+                write_stats(os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("stats")
-        else:
-            print(f"Found stats at {cached_stats}")
-            with open(cached_stats, "rb") as fh:
-                stats = pickle.load(fh)
+        if measure:
+            if labels_dev is None:
+                labels_dev = cached_labels_to_device()
+            stats.update(finish_intensity(_intensity_of(eng, labels_dev, raw_vol[:Z], N), stats["voxel_counts"]))
+            # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
+            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
+            mark("intensity")
     except BaseException:
         try:
             wait()  # (do not leave the writer thread behind an error of this one)

@@ -661,6 +661,39 @@ class HipEngine:
         self._leave()
         return int(kept.value)
 
+    def cc_intensity(self, labels, raw, n: int) -> dict:
+        """Per-label statistics of the raw volume under a label volume (dlv_cc_intensity_dev).  labels: int32 (uint32 payload)
+        (Z,Y,X) in HBM; raw: uint16 (or int16-viewed) (Zr,Yr,Xr) in HBM with Zr >= Z, Yr >= Y, Xr >= X, contiguous in its last
+        axis - voxel (z,y,x) of the labels is raw[z,y,x], the pitches come from raw's strides (the padded network input, or a view
+        into it).  -> {"intensity_sum", "intensity_sumsq": uint64, "intensity_min", "intensity_max": uint16}, n+1 rows each; a label
+        without a voxel - and row 0 - reads 0, 0, 0xFFFF, 0."""
+        torch = self.torch
+        for name, t, dtypes in (("labels", labels, (torch.int32,)), ("raw", raw, (torch.uint16, torch.int16))):
+            if not isinstance(t, torch.Tensor) or t.device != self.device:
+                raise ValueError(f"cc_intensity: {name}: expected a torch tensor on {self.device}, got {type(t).__name__} on "
+                                 f"{getattr(t, 'device', None)}")
+            if t.dtype not in dtypes or t.dim() != 3:
+                raise ValueError(f"cc_intensity: {name}: expected a 3-D tensor of {' / '.join(str(d) for d in dtypes)}, got "
+                                 f"{t.dim()}-D {t.dtype}")
+        if not labels.is_contiguous() or labels.numel() == 0:
+            raise ValueError(f"cc_intensity: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
+        Z, Y, X = (int(v) for v in labels.shape)
+        if any(r < v for r, v in zip(raw.shape, (Z, Y, X))):
+            raise ValueError(f"cc_intensity: raw of shape {tuple(raw.shape)} is smaller than the labels {(Z, Y, X)}")
+        pitch_z, pitch_y, pitch_x = (int(s) for s in raw.stride())
+        if pitch_x != 1 or pitch_y < X or pitch_z < Y * pitch_y:
+            raise ValueError(f"cc_intensity: raw with strides {tuple(raw.stride())} is not a (padded) volume with a contiguous last axis")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"cc_intensity: n = {n}")
+        out = {"intensity_sum": np.zeros(n + 1, dtype=np.uint64), "intensity_sumsq": np.zeros(n + 1, dtype=np.uint64),
+               "intensity_min": np.zeros(n + 1, dtype=np.uint16), "intensity_max": np.zeros(n + 1, dtype=np.uint16)}
+        self._enter()
+        self._check(self.lib.dlv_cc_intensity_dev(self.ctx, C.c_void_p(labels.data_ptr()), C.c_void_p(raw.data_ptr()), Z, Y, X,
+                                                  pitch_y, pitch_z, n, *(a.ctypes.data_as(C.c_void_p) for a in out.values())))
+        self._leave()
+        return out
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

@@ -81,6 +81,75 @@ def size_filter_bounds(settings, min_size, max_size) -> Optional[Tuple[int, int]
     return lo, hi
 
 
+INTENSITY_KEYS = ("intensity_sum", "intensity_sumsq", "intensity_min", "intensity_max")  # what HipEngine.cc_intensity returns
+INTENSITY_ABSENT_MIN = 0xFFFF  # intensity_min of a label without a voxel (with sum 0, sumsq 0, max 0)
+
+
+def intensity_stats_enabled(settings) -> bool:
+    """count_blobs' per-cell raw intensity statistics: on only for a truthy settings["mi355x"]["intensity_stats"]."""
+    return bool(((settings or {}).get("mi355x") or {}).get("intensity_stats"))
+
+
+def merge_intensity(parts) -> dict:
+    """Per-slab dicts of HipEngine.cc_intensity over the same labels 0..n -> the dict of the whole volume: sums add, minima /
+    maxima combine (an absent label is 0, 0, 0xFFFF, 0 - the neutral element of all four).  None entries (empty slabs) are
+    skipped; with nothing left, or rows that disagree, ValueError."""
+    parts = [p for p in parts if p is not None]
+    if not parts:
+        raise ValueError("merge_intensity: no slab to merge")
+    rows = len(parts[0]["intensity_sum"])
+    if any(len(p[k]) != rows for p in parts for k in INTENSITY_KEYS):
+        raise ValueError("merge_intensity: the slabs do not cover the same labels")
+    out = {"intensity_sum": np.zeros(rows, dtype=np.uint64), "intensity_sumsq": np.zeros(rows, dtype=np.uint64),
+           "intensity_min": np.full(rows, INTENSITY_ABSENT_MIN, dtype=np.uint16), "intensity_max": np.zeros(rows, dtype=np.uint16)}
+    for p in parts:
+        out["intensity_sum"] += np.asarray(p["intensity_sum"], dtype=np.uint64)
+        out["intensity_sumsq"] += np.asarray(p["intensity_sumsq"], dtype=np.uint64)
+        np.minimum(out["intensity_min"], np.asarray(p["intensity_min"], dtype=np.uint16), out=out["intensity_min"])
+        np.maximum(out["intensity_max"], np.asarray(p["intensity_max"], dtype=np.uint16), out=out["intensity_max"])
+    return out
+
+
+def finish_intensity(merged: dict, voxel_counts) -> dict:
+    """The whole-volume accumulators (HipEngine.cc_intensity / merge_intensity) -> what count_blobs stores: the four arrays with
+    row 0's minimum set to 0 (the background is not measured: its row is all zeros) and intensity_mean, float64 sum / count (0.0
+    where the count is 0).  A label 1..n that reads as absent (sum 0, sumsq 0, min 0xFFFF, max 0) while cc_stats counted voxels
+    for it, or that was measured while its count is 0, means labels and raw volume do not belong together: RuntimeError."""
+    counts = np.asarray(voxel_counts)
+    out = {k: np.array(merged[k], dtype=np.uint16 if k in ("intensity_min", "intensity_max") else np.uint64) for k in INTENSITY_KEYS}
+    rows = len(out["intensity_sum"])
+    if len(counts) != rows or rows < 1:
+        raise RuntimeError(f"intensity statistics of {rows} rows beside voxel counts of {len(counts)}")
+    absent = ((out["intensity_sum"] == 0) & (out["intensity_sumsq"] == 0) & (out["intensity_min"] == INTENSITY_ABSENT_MIN)
+              & (out["intensity_max"] == 0))
+    bad = np.flatnonzero(absent[1:] != (counts[1:] == 0)) + 1
+    if len(bad):
+        l = int(bad[0])
+        raise RuntimeError(f"intensity statistics and voxel counts disagree on {len(bad)} label(s), first label {l}: "
+                           f"{int(counts[l])} voxels counted, {'none' if absent[l] else 'some'} measured - labels and raw volume of different brains?")
+    out["intensity_min"][0] = 0
+    mean = np.zeros(rows, dtype=np.float64)
+    np.divide(out["intensity_sum"].astype(np.float64), counts.astype(np.float64), out=mean, where=counts != 0)
+    mean[0] = 0.0  # (row 0's count is the background's, its sum is not taken)
+    out["intensity_mean"] = mean
+    return out
+
+
+def cell_intensity_csv_text(stats: dict, n: int) -> str:
+    """count_blobs' cell_intensity/<brain>.csv: header ``Blob,Size,Min,Max,Sum,SumSq,Mean``, one row per label 1..N - all N:
+    this table has no reference to mirror, so none of its quirks (cells_csv_text drops the last label) - integers written
+    plainly, Mean as repr of the float64 value, every line ended by a newline."""
+    n = int(n)
+    cols = [np.asarray(stats[k])[1:n + 1].tolist() for k in ("voxel_counts", "intensity_min", "intensity_max", "intensity_sum",
+                                                              "intensity_sumsq")]
+    mean = np.asarray(stats["intensity_mean"], dtype=np.float64)[1:n + 1].tolist()
+    if any(len(c) != n for c in cols) or len(mean) != n:
+        raise ValueError("statistics shorter than the label count")
+    lines = ["Blob,Size,Min,Max,Sum,SumSq,Mean"]
+    lines.extend(f"{i},{c},{lo},{hi},{s},{q},{m!r}" for i, (c, lo, hi, s, q, m) in enumerate(zip(*cols, mean), 1))
+    return "\n".join(lines) + "\n"
+
+
 def pass_schedule(tta: bool) -> List[Tuple[Optional[int], int]]:
     """(flip_dim, repeat) per DISTINCT pass.  The reference runs 1 plain pass, then 4 x {noise,
     noise + flip Z (dim 2), noise + flip Y (dim 3)} (inference/inference.py:261-279); its noise is

@@ -299,6 +299,15 @@ int dlv_cc_stats_raw_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y,
 int dlv_cc_counts_dev(dlv_ctx* ctx, const uint32_t* labels_dev, uint64_t nvox, uint64_t n, uint32_t* counts_dev);
 int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, uint64_t n, const uint32_t* counts_dev,
                            int64_t min_size, int64_t max_size, uint64_t* n_kept_out);
+/* Per-label statistics of a raw uint16 volume under a label volume (no counterpart in the reference).
+ * labels_dev: uint32 (Z,Y,X) contiguous, labels 0..n; raw_dev: uint16, voxel (z,y,x) at raw_dev[z*raw_pitch_z + y*raw_pitch_y + x]
+ * (pitches in elements: the raw file is padded to window multiples, the labels are not). Host outputs of n+1 rows:
+ * sum, sumsq uint64 (exact), vmin, vmax uint16. A label with no voxel in this volume: sum 0, sumsq 0, vmin 0xFFFF, vmax 0 -
+ * so two slabs merge with +, +, min, max. Row 0 (background) is not measured and always reads like an absent label. Labels above n
+ * are not accumulated. raw_pitch_y < X, raw_pitch_z < Y*raw_pitch_y, a NULL pointer or Z/Y/X < 1: DLV_EINVAL. Synchronous. */
+int dlv_cc_intensity_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
+                         int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n,
+                         uint64_t* sum, uint64_t* sumsq, uint16_t* vmin, uint16_t* vmax);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

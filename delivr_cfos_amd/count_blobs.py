@@ -14,10 +14,16 @@ import pickle
 import numpy as np
 
 from . import hostio
-from .hostlogic import (INTENSITY_KEYS, cell_intensity_csv_text, cells_csv_bytes, csv_name, finish_intensity, intensity_stats_enabled,
-                        merge_intensity, size_filter_bounds)
+from .hostlogic import (INTENSITY_KEYS, SHELL_KEYS, background_shell_radius, cell_intensity_csv_text, cells_csv_bytes, csv_name,
+                        finish_intensity, finish_shell, intensity_stats_enabled, merge_intensity, merge_shell, size_filter_bounds)
 
 _INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
+_SHELL_STATS_KEYS = SHELL_KEYS + ("shell_radius",)  # ... and settings["mi355x"]["background_shell"]
+
+
+def _shell_bytes_per_voxel(radius: int) -> int:
+    """HBM of HipEngine.cc_shell beside the labels and the raw volume: the shell volume, and the scratch volume above radius 1"""
+    return 0 if not radius else (4 if radius == 1 else 8)
 
 
 def _find_cached(path: str, suffix: str, brain: str):
@@ -100,34 +106,83 @@ def _open_raw_volume(settings, brain, shape):
     return vol, path
 
 
-def _intensity_of(eng, labels_dev, raw_planes, N):
+def _shell_of(eng, labels_dev, raw_dev, N, radius, keep=None):
+    """the shells of radius `radius` around the cells of labels_dev, measured: (HipEngine.cc_intensity's dict of the shell volume,
+    its voxel counts per label 0..N as uint32) - hostlogic.finish_shell's / merge_shell's input.  keep: (first, planes) - the
+    planes of labels_dev whose shell counts (a slab extended by its neighbours' planes: the shell of the slab alone)"""
+    shell = eng.cc_shell(labels_dev, radius, raw_dev)
+    if keep is not None:
+        shell, raw_dev = shell[keep[0]:keep[0] + keep[1]], raw_dev[keep[0]:keep[0] + keep[1]]
+    return eng.cc_intensity(shell, raw_dev, N), eng.cc_counts(shell, N).cpu().numpy().view(np.uint32)
+
+
+def _intensity_of(eng, labels_dev, raw_planes, N, cells=True, shell_radius=0):
     """raw_planes: the planes of the raw memmap that lie under labels_dev (whole planes: the Y / X padding stays, the pitches
-    describe it) -> HipEngine.cc_intensity's dict; the raw tensor is gone when this returns"""
+    describe it), uploaded once -> (HipEngine.cc_intensity's dict of the cells, or None without `cells`; _shell_of's pair, or
+    None with shell_radius 0); the raw tensor is gone when this returns"""
     raw_dev = hostio.upload(eng, raw_planes, what="h2d_raw")
     try:
-        return eng.cc_intensity(labels_dev, raw_dev, N)
+        part = eng.cc_intensity(labels_dev, raw_dev, N) if cells else None
+        return part, (_shell_of(eng, labels_dev, raw_dev, N, shell_radius) if shell_radius else None)
     finally:
         del raw_dev
 
 
-def _write_intensity_table(path_out, brain, stats, N, raw_file):
+def _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, radius):
+    """_intensity_of for the slab [lo, hi) of a sharded run.  The shell of a voxel depends on the labels within `radius` planes
+    of it only, so every rank takes `radius` planes of the final global labels from either neighbour (exchanged as
+    parallel.ccl_sharded exchanges its boundary plane), expands the extended slab and keeps its own planes - exactly the
+    planes [lo, hi) of the whole volume's shell.  Every slab holds at least `radius` planes (count_blobs checked)."""
+    import torch
+
+    from .parallel import _needs_host_staging
+
+    if not radius:
+        return _intensity_of(eng, labels, raw_vol[lo:hi], N)
+    stage = _needs_host_staging(labels, dist)
+    ops, got = [], {}
+    for peer, mine in ((rank - 1, labels[:radius]), (rank + 1, labels[-radius:])):
+        if 0 <= peer < world:
+            t = mine.contiguous()
+            ops.append(dist.P2POp(dist.isend, t.cpu() if stage else t, peer))
+            got[peer] = torch.empty_like(t, device="cpu") if stage else torch.empty_like(t)
+            ops.append(dist.P2POp(dist.irecv, got[peer], peer))
+    for req in dist.batch_isend_irecv(ops):
+        req.wait()
+    up, down = got.get(rank - 1), got.get(rank + 1)
+    extended = torch.cat([t.to(labels.device) for t in (up, labels, down) if t is not None])
+    del up, down, got
+    first = radius if rank > 0 else 0
+    raw_dev = hostio.upload(eng, raw_vol[lo - first:lo - first + int(extended.shape[0])], what="h2d_raw")
+    try:
+        part = eng.cc_intensity(labels, raw_dev[first:first + (hi - lo)], N)
+        return part, _shell_of(eng, extended, raw_dev, N, radius, keep=(first, hi - lo))
+    finally:
+        del raw_dev
+
+
+def _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius=0):
     """<output_location>/cell_intensity/<brain>.csv - in a sub-folder, so that no cache look-up (_find_cached: any entry with
     '.npy' / '.pickle' and the brain's name) and no reader of the reference's CSV ever matches it"""
     folder = os.path.join(path_out, "cell_intensity")
     os.makedirs(folder, exist_ok=True)
     with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
-        fh.write(cell_intensity_csv_text(stats, N))
+        # (shell entries of a cached pickle do not reach the table of a run without the key)
+        fh.write(cell_intensity_csv_text(stats if shell_radius else {k: v for k, v in stats.items() if k not in SHELL_KEYS}, N))
     count_blobs.last_intensity = {"n": int(N), "raw_file": raw_file}
+    if shell_radius:
+        count_blobs.last_intensity["shell_radius"] = int(shell_radius)
 
 
-def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_vol=None):
+def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_vol=None, shell_radius=0):
     """One process per GPU: every rank labels a Z-slab of the mask, seams are merged (parallel.ccl_sharded) and every
     rank writes ITS label slab straight into the output .npy (rank 0 creates the file once N - and with it the label
     dtype - is known); only the merged statistics travel to rank 0.  No rank ever holds the whole label volume (17 GB for
     1024x2048x2048).  bounds: the size filter (hostlogic.size_filter_bounds) - every rank counts the voxels of the global
     labels in its slab, the counts are summed over the ranks, every rank applies the same filter to its slab and the
     statistics are taken on the filtered labels.  raw_vol: the raw volume (settings["mi355x"]["intensity_stats"]) - every
-    rank measures planes [lo, hi) of it under its final global labels, rank 0 merges the parts into its stats.
+    rank measures planes [lo, hi) of it under its final global labels, rank 0 merges the parts into its stats.  shell_radius:
+    settings["mi355x"]["background_shell"] - the shells around the cells are measured too (_intensity_and_shell_of_slab).
     Returns (N, stats | None)."""
     from .parallel import ccl_sharded, merge_stats
 
@@ -180,7 +235,7 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
         part, failed = None, None
         try:
             if labels is not None:
-                part = _intensity_of(eng, labels, raw_vol[lo:hi], N)
+                part = _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, shell_radius)
         except Exception as exc:
             failed = f"rank {rank}: {exc!r}"
         _raise_if_any_failed(dist, failed, "count_blobs: the intensity statistics")
@@ -189,7 +244,10 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
         failed = None
         if rank == 0:
             try:
-                stats.update(finish_intensity(merge_intensity(parts), stats["voxel_counts"]))
+                stats.update(finish_intensity(merge_intensity([p and p[0] for p in parts]), stats["voxel_counts"]))
+                if shell_radius:
+                    stats.update(finish_shell(*merge_shell([p and p[1] for p in parts]), stats["intensity_mean"]))
+                    stats["shell_radius"] = int(shell_radius)
             except Exception as exc:
                 failed = f"rank 0: {exc!r}"
         _raise_if_any_failed(dist, failed, "count_blobs: merging the intensity statistics")
@@ -251,10 +309,20 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     become keys of <brain>-stats.pickle (intensity_sum / _sumsq / _min / _max / _mean, N+1 rows, row 0 zero), the table goes to
     <output_location>/cell_intensity/<brain>.csv and ``count_blobs.last_intensity`` holds {"n", "raw_file"}.  Cached labels are
     measured too, and a cached pickle without the keys is rewritten with them.  A missing or too small raw volume is an error
-    before any file is written; a mask that needs the slab-streamed path is refused.  Off or absent: nothing of this happens."""
+    before any file is written; a mask that needs the slab-streamed path is refused.  Off or absent: nothing of this happens.
+
+    ``settings["mi355x"]["background_shell"]`` = r (1..16, with intensity_stats on): every cell's local background is measured as
+    well.  The final labels are expanded by r synchronous steps of a 26-neighbourhood minimum (a background voxel goes to the
+    smallest label among the cells nearest to it in Chebyshev distance, if that is at most r); the expanded voxels that belong to no
+    cell and are not 0 in the raw volume (0 is "outside the tissue") are the cell's shell.  The pickle gains shell_voxels, shell_sum /
+    _sumsq / _min / _max / _mean, contrast (= intensity_mean / shell_mean; 0.0 for a cell without a shell) and shell_radius, the table
+    the matching columns and ``count_blobs.last_intensity`` "shell_radius".  A cached pickle without these keys, or with another
+    shell_radius, is completed.  Needs 4 (r = 1) or 8 more bytes of HBM per voxel; under torch.distributed every slab must hold at
+    least r planes.  Off, 0 or absent: nothing of this happens."""
     from .engine import shared_engine
 
     bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
+    shell_radius = background_shell_radius(settings)  # (raises on a bad value, or without intensity_stats, before any file is touched)
     count_blobs.last_filter = None  # set by a run that filtered
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     if bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
@@ -269,6 +337,12 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     rank = dist.get_rank() if sharded else 0
 
     shape = tuple(int(v) for v in stack_shape[2:])
+    if sharded and shell_radius:
+        # every rank computes the same slabs: all raise, before any collective, or none does
+        thin = [hi - lo for lo, hi in _even_slabs(shape[0], dist.get_world_size()) if hi - lo < shell_radius]
+        if thin:
+            raise ValueError(f"count_blobs: settings['mi355x']['background_shell'] = {shell_radius} needs Z-slabs of at least {shell_radius} "
+                             f"planes on every rank, {shape[0]} planes over {dist.get_world_size()} ranks give slabs of {min(thin)}")
     raw_vol, raw_file = None, None
     if intensity_stats_enabled(settings):  # (before any file is written; under torch.distributed all ranks raise or none does)
         failed = None
@@ -303,7 +377,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
             raise RuntimeError(f"count_blobs: rank 0 failed while looking for a cached labelling: {branch[0][1]}")
         if not branch[0][1]:
             try:
-                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds, raw_vol)
+                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds, raw_vol, shell_radius)
             finally:
                 if own:
                     eng.close()
@@ -315,7 +389,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
                     with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
                         fh.write(cells_csv_bytes(stats, N))
                     if raw_vol is not None:
-                        _write_intensity_table(path_out, brain, stats, N, raw_file)
+                        _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
                     end = datetime.datetime.now()
                     print(f"{end} {brain} {brain_i} / {len_b} Done ({dist.get_world_size()} ranks); Took {end - start}")
                 except Exception as exc:
@@ -336,12 +410,12 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     try:
         import time
 
-        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol)
+        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol, shell_radius)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
         if raw_vol is not None:
-            _write_intensity_table(path_out, brain, stats, N, raw_file)
+            _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
         count_blobs.last_timings["csv_s"] = time.perf_counter() - t_csv
         t_join = time.perf_counter()
         if defer_write:
@@ -361,12 +435,13 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None):
+def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
     made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
     filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write.  raw_vol: the
-    raw volume (settings["mi355x"]["intensity_stats"]), measured under the labels - fresh or cached - after cc_stats."""
+    raw volume (settings["mi355x"]["intensity_stats"]), measured under the labels - fresh or cached - after cc_stats.
+    shell_radius: settings["mi355x"]["background_shell"] - the shells around the cells are measured with the same raw tensor."""
     import time
 
     labels_dev = None
@@ -391,6 +466,12 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                               f"volume in HBM ({int(bin_img.size) * (ccl_bytes_per_voxel() + 2) / 2**30:.1f} GiB), the HBM budget is "
                               f"{budget / 2**30:.1f} GiB and the slab-streamed labelling does not measure; raise "
                               "settings['mi355x']['hbm_budget_gb'] or switch intensity_stats off")
+        shell_bpv = _shell_bytes_per_voxel(shell_radius)
+        if shell_bpv and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv) > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['background_shell'] = {shell_radius} needs {shell_bpv} more bytes "
+                              f"per voxel in HBM beside the mask, its labels and the raw volume "
+                              f"({int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv) / 2**30:.1f} GiB), the HBM budget is "
+                              f"{budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
         if not cached and need > budget:
             # the mask + its uint32 labels do not fit this GPU: Z-slabs through the device, seams merged on the host
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
@@ -478,17 +559,25 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             with open(path, "wb") as fh:
                 pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
 
-        have_intensity = False
+        have_intensity = have_shell = False
         if cached_stats:
             print(f"Found stats at {cached_stats}")
             with open(cached_stats, "rb") as fh:
                 stats = pickle.load(fh)
             have_intensity = all(k in stats for k in _INTENSITY_STATS_KEYS)
-        measure = raw_vol is not None and not have_intensity
+            # (complete only with every shell key and the radius asked for)
+            have_shell = all(k in stats for k in _SHELL_STATS_KEYS) and stats["shell_radius"] == shell_radius
+        measure_cells = raw_vol is not None and not have_intensity
+        measure_shell = raw_vol is not None and shell_radius > 0 and not have_shell
+        measure = measure_cells or measure_shell
         if measure and labels_dev is None and int(labels.size) * (4 + 2) > budget:
             raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_stats'] needs the cached labels and the raw volume "
                               f"in HBM ({int(labels.size) * 6 / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
                               "settings['mi355x']['hbm_budget_gb'] or switch intensity_stats off")
+        if measure_shell and labels_dev is None and int(labels.size) * (4 + 2 + shell_bpv) > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['background_shell'] = {shell_radius} needs {shell_bpv} more bytes "
+                              f"per voxel in HBM beside the cached labels and the raw volume ({int(labels.size) * (6 + shell_bpv) / 2**30:.1f} GiB), "
+                              f"the HBM budget is {budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
         if not cached_stats:
             if labels_dev is None and int(labels.size) * 4 > budget:
                 # cached labels that do not fit the HBM budget: statistics slab by slab (raw sums add up; streaming.py)
@@ -505,7 +594,12 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
         if measure:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
-            stats.update(finish_intensity(_intensity_of(eng, labels_dev, raw_vol[:Z], N), stats["voxel_counts"]))
+            part, shell_part = _intensity_of(eng, labels_dev, raw_vol[:Z], N, cells=measure_cells, shell_radius=shell_radius if measure_shell else 0)
+            if measure_cells:
+                stats.update(finish_intensity(part, stats["voxel_counts"]))
+            if measure_shell:
+                stats.update(finish_shell(*shell_part, stats["intensity_mean"]))
+                stats["shell_radius"] = int(shell_radius)
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
             write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")

@@ -694,6 +694,45 @@ class HipEngine:
         self._leave()
         return out
 
+    def cc_shell(self, labels, radius: int, raw=None):
+        """The background shell of every component (dlv_cc_shell_dev): the labels are expanded into the background by `radius`
+        (1..16) synchronous steps of a 26-neighbourhood minimum - a voxel goes to the smallest label among the cells nearest to
+        it in Chebyshev distance - and the expanded voxels that are background in `labels` and not 0 in `raw` are the shell.
+        labels, raw: as for cc_intensity; raw None: no raw condition (labels + shell are then the expanded labels).  -> int32
+        tensor (uint32 payload) of the labels' shape in HBM; cc_intensity / cc_counts on it measure the shells.  Needs one more
+        volume of that size while it runs when radius > 1."""
+        torch = self.torch
+        for name, t, dtypes in (("labels", labels, (torch.int32,)), ("raw", raw, (torch.uint16, torch.int16))):
+            if t is None and name == "raw":
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != self.device:
+                raise ValueError(f"cc_shell: {name}: expected a torch tensor on {self.device}, got {type(t).__name__} on "
+                                 f"{getattr(t, 'device', None)}")
+            if t.dtype not in dtypes or t.dim() != 3:
+                raise ValueError(f"cc_shell: {name}: expected a 3-D tensor of {' / '.join(str(d) for d in dtypes)}, got "
+                                 f"{t.dim()}-D {t.dtype}")
+        if not labels.is_contiguous() or labels.numel() == 0:
+            raise ValueError(f"cc_shell: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
+        Z, Y, X = (int(v) for v in labels.shape)
+        pitch_z = pitch_y = 0
+        if raw is not None:
+            if any(r < v for r, v in zip(raw.shape, (Z, Y, X))):
+                raise ValueError(f"cc_shell: raw of shape {tuple(raw.shape)} is smaller than the labels {(Z, Y, X)}")
+            pitch_z, pitch_y, pitch_x = (int(s) for s in raw.stride())
+            if pitch_x != 1 or pitch_y < X or pitch_z < Y * pitch_y:
+                raise ValueError(f"cc_shell: raw with strides {tuple(raw.stride())} is not a (padded) volume with a contiguous last axis")
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 16:
+            raise ValueError(f"cc_shell: radius = {radius!r}: expected an integer 1..16")
+        radius = int(radius)
+        shell = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
+        scratch = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device) if radius > 1 else None
+        self._enter()
+        self._check(self.lib.dlv_cc_shell_dev(self.ctx, C.c_void_p(labels.data_ptr()), C.c_void_p(raw.data_ptr()) if raw is not None else None,
+                                              Z, Y, X, pitch_y, pitch_z, radius, C.c_void_p(shell.data_ptr()),
+                                              C.c_void_p(scratch.data_ptr()) if scratch is not None else None))
+        self._leave()  # (torch's stream now waits for the sweeps: the scratch volume freed here is not reused before them)
+        return shell
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

@@ -135,18 +135,98 @@ def finish_intensity(merged: dict, voxel_counts) -> dict:
     return out
 
 
+SHELL_KEYS = ("shell_voxels", "shell_sum", "shell_sumsq", "shell_min", "shell_max", "shell_mean", "contrast")  # finish_shell's keys
+SHELL_MAX_RADIUS = 16  # dlv_cc_shell_dev's largest radius
+
+
+def background_shell_radius(settings) -> int:
+    """count_blobs' per-cell local background: 0 when settings["mi355x"]["background_shell"] is absent, false or 0, else the
+    shell radius in voxels, an integer 1..16.  ValueError for anything else (true, a float, a string, a value outside the
+    range) and for a radius without settings["mi355x"]["intensity_stats"]: the shell is measured beside the cells."""
+    value = ((settings or {}).get("mi355x") or {}).get("background_shell")
+    if value is None or value is False or (not isinstance(value, bool) and isinstance(value, (int, np.integer)) and int(value) == 0):
+        return 0
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= SHELL_MAX_RADIUS:
+        raise ValueError(f"settings['mi355x']['background_shell'] = {value!r}: expected a shell radius in voxels, an integer "
+                         f"1..{SHELL_MAX_RADIUS} (0 / false: off)")
+    if not intensity_stats_enabled(settings):
+        raise ValueError(f"settings['mi355x']['background_shell'] = {int(value)} needs settings['mi355x']['intensity_stats']: the shell is "
+                         "measured beside the cells")
+    return int(value)
+
+
+def merge_shell(parts):
+    """Per-slab (HipEngine.cc_intensity dict of the shell volume, its uint32 voxel counts per label) -> the pair of the whole
+    volume: merge_intensity plus a sum of the counts.  None entries (empty slabs) are skipped."""
+    parts = [p for p in parts if p is not None]
+    merged = merge_intensity([p[0] for p in parts])
+    rows = len(merged["intensity_sum"])
+    counts = np.zeros(rows, dtype=np.uint64)
+    for _, c in parts:
+        if len(c) != rows:
+            raise ValueError("merge_shell: the slabs do not cover the same labels")
+        counts += np.asarray(c, dtype=np.uint64)
+    return merged, counts
+
+
+def finish_shell(parts: dict, shell_counts, intensity_mean) -> dict:
+    """The accumulators of the shell volume (HipEngine.cc_intensity on HipEngine.cc_shell's result, or merge_shell's) with the
+    shell's voxel counts per label (cc_counts) and the cells' intensity_mean -> what count_blobs stores, N+1 rows each, row 0 all
+    zeros: shell_voxels uint32, shell_sum / shell_sumsq uint64, shell_min / shell_max uint16 (0 for a cell without a shell),
+    shell_mean float64 = sum / voxels and contrast float64 = intensity_mean / shell_mean (both 0.0 without a shell; a shell
+    voxel is not 0 in the raw volume, so the mean of a shell with a voxel is positive).  RuntimeError when a label was measured
+    and not counted, or counted and not measured."""
+    counts = np.asarray(shell_counts).astype(np.uint64)
+    cells = np.asarray(intensity_mean, dtype=np.float64)
+    rows = len(counts)
+    if rows < 1 or len(cells) != rows or any(len(parts[k]) != rows for k in INTENSITY_KEYS):
+        raise RuntimeError(f"shell statistics of {[len(parts[k]) for k in INTENSITY_KEYS]} rows beside shell counts of {rows} and "
+                           f"cell means of {len(cells)}")
+    if int(counts.max()) > 0xFFFFFFFF:
+        raise RuntimeError("a shell of more than 2^32 - 1 voxels")
+    counts = counts.copy()
+    counts[0] = 0  # (row 0 of cc_counts is the voxels outside every shell)
+    s, q = np.array(parts["intensity_sum"], dtype=np.uint64), np.array(parts["intensity_sumsq"], dtype=np.uint64)
+    lo, hi = np.array(parts["intensity_min"], dtype=np.uint16), np.array(parts["intensity_max"], dtype=np.uint16)
+    absent = (s == 0) & (q == 0) & (lo == INTENSITY_ABSENT_MIN) & (hi == 0)
+    bad = np.flatnonzero(absent[1:] != (counts[1:] == 0)) + 1
+    if len(bad):
+        l = int(bad[0])
+        raise RuntimeError(f"shell statistics and shell counts disagree on {len(bad)} label(s), first label {l}: "
+                           f"{int(counts[l])} voxels counted, {'none' if absent[l] else 'some'} measured")
+    lo[absent] = 0
+    for a in (s, q, lo, hi):
+        a[0] = 0
+    mean = np.zeros(rows, dtype=np.float64)
+    np.divide(s.astype(np.float64), counts.astype(np.float64), out=mean, where=counts != 0)
+    contrast = np.zeros(rows, dtype=np.float64)
+    np.divide(cells, mean, out=contrast, where=counts != 0)
+    return {"shell_voxels": counts.astype(np.uint32), "shell_sum": s, "shell_sumsq": q, "shell_min": lo, "shell_max": hi,
+            "shell_mean": mean, "contrast": contrast}
+
+
 def cell_intensity_csv_text(stats: dict, n: int) -> str:
     """count_blobs' cell_intensity/<brain>.csv: header ``Blob,Size,Min,Max,Sum,SumSq,Mean``, one row per label 1..N - all N:
     this table has no reference to mirror, so none of its quirks (cells_csv_text drops the last label) - integers written
-    plainly, Mean as repr of the float64 value, every line ended by a newline."""
+    plainly, Mean as repr of the float64 value, every line ended by a newline.  With finish_shell's keys in `stats` (all of
+    them) the columns ``ShellSize,ShellMin,ShellMax,ShellSum,ShellSumSq,ShellMean,Contrast`` follow Mean, floats as repr."""
     n = int(n)
     cols = [np.asarray(stats[k])[1:n + 1].tolist() for k in ("voxel_counts", "intensity_min", "intensity_max", "intensity_sum",
                                                               "intensity_sumsq")]
     mean = np.asarray(stats["intensity_mean"], dtype=np.float64)[1:n + 1].tolist()
     if any(len(c) != n for c in cols) or len(mean) != n:
         raise ValueError("statistics shorter than the label count")
-    lines = ["Blob,Size,Min,Max,Sum,SumSq,Mean"]
-    lines.extend(f"{i},{c},{lo},{hi},{s},{q},{m!r}" for i, (c, lo, hi, s, q, m) in enumerate(zip(*cols, mean), 1))
+    if not all(k in stats for k in SHELL_KEYS):
+        lines = ["Blob,Size,Min,Max,Sum,SumSq,Mean"]
+        lines.extend(f"{i},{c},{lo},{hi},{s},{q},{m!r}" for i, (c, lo, hi, s, q, m) in enumerate(zip(*cols, mean), 1))
+        return "\n".join(lines) + "\n"
+    cols += [np.asarray(stats[k])[1:n + 1].tolist() for k in ("shell_voxels", "shell_min", "shell_max", "shell_sum", "shell_sumsq")]
+    floats = [np.asarray(stats[k], dtype=np.float64)[1:n + 1].tolist() for k in ("shell_mean", "contrast")]
+    if any(len(c) != n for c in cols + floats):
+        raise ValueError("statistics shorter than the label count")
+    lines = ["Blob,Size,Min,Max,Sum,SumSq,Mean,ShellSize,ShellMin,ShellMax,ShellSum,ShellSumSq,ShellMean,Contrast"]
+    lines.extend(f"{i},{c},{lo},{hi},{s},{q},{m!r},{sc},{slo},{shi},{ss},{sq},{sm!r},{ct!r}"
+                 for i, (c, lo, hi, s, q, sc, slo, shi, ss, sq, m, sm, ct) in enumerate(zip(*cols, mean, *floats), 1))
     return "\n".join(lines) + "\n"
 
 

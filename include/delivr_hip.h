@@ -308,6 +308,16 @@ int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, ui
 int dlv_cc_intensity_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
                          int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n,
                          uint64_t* sum, uint64_t* sumsq, uint16_t* vmin, uint16_t* vmax);
+/* The background shell of every component (no counterpart in the reference): E_0 = labels; E_{k+1}(v) = E_k(v) where that is not
+ * 0, else the smallest non-zero E_k over the 26 neighbours of v inside the volume (0 without one), every step from E_k alone;
+ * shell(v) = E_radius(v) where labels(v) == 0 and raw(v) != 0, else 0 - the smallest label among the cells nearest to v in
+ * Chebyshev distance, when that distance is at most radius. dlv_cc_intensity_dev / dlv_cc_counts_dev on shell_dev measure it.
+ * labels_dev (not modified), raw_dev and the pitches as for dlv_cc_intensity_dev; raw_dev may be NULL: the raw != 0 condition is
+ * dropped (labels_dev + shell_dev are then the expanded labels). shell_dev: Z*Y*X uint32, fully written. scratch_dev: a second
+ * volume of that size, may be NULL with radius 1. radius outside 1..16, a NULL pointer, Z/Y/X < 1, bad pitches, a misaligned
+ * pointer (4 / 2 bytes) or labels_dev / shell_dev / scratch_dev overlapping: DLV_EINVAL. Asynchronous on the context's stream. */
+int dlv_cc_shell_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
+                     int64_t raw_pitch_y, int64_t raw_pitch_z, int radius, uint32_t* shell_dev, uint32_t* scratch_dev);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

@@ -14,8 +14,9 @@ import pickle
 import numpy as np
 
 from . import hostio
-from .hostlogic import (INTENSITY_KEYS, SHELL_KEYS, background_shell_radius, cell_intensity_csv_text, cells_csv_bytes, csv_name,
-                        finish_intensity, finish_shell, intensity_stats_enabled, merge_intensity, merge_shell, size_filter_bounds)
+from .hostlogic import (INTENSITY_KEYS, SHAPE_KEYS, SHELL_KEYS, background_shell_radius, cell_intensity_csv_text, cell_shape_csv_text,
+                        cells_csv_bytes, csv_name, finish_intensity, finish_shape, finish_shell, intensity_stats_enabled, merge_intensity,
+                        merge_shape, merge_shell, shape_stats_enabled, size_filter_bounds)
 
 _INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
 _SHELL_STATS_KEYS = SHELL_KEYS + ("shell_radius",)  # ... and settings["mi355x"]["background_shell"]
@@ -128,17 +129,14 @@ def _intensity_of(eng, labels_dev, raw_planes, N, cells=True, shell_radius=0):
         del raw_dev
 
 
-def _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, radius):
-    """_intensity_of for the slab [lo, hi) of a sharded run.  The shell of a voxel depends on the labels within `radius` planes
-    of it only, so every rank takes `radius` planes of the final global labels from either neighbour (exchanged as
-    parallel.ccl_sharded exchanges its boundary plane), expands the extended slab and keeps its own planes - exactly the
-    planes [lo, hi) of the whole volume's shell.  Every slab holds at least `radius` planes (count_blobs checked)."""
+def _slab_with_neighbour_planes(labels, dist, rank, world, radius):
+    """The slab `labels` of a sharded run extended by `radius` planes of the final global labels from either neighbour slab
+    (exchanged as parallel.ccl_sharded exchanges its boundary plane) -> (extended slab, index of the slab's first plane in it:
+    `radius`, or 0 on rank 0).  Every slab holds at least `radius` planes (count_blobs checked)."""
     import torch
 
     from .parallel import _needs_host_staging
 
-    if not radius:
-        return _intensity_of(eng, labels, raw_vol[lo:hi], N)
     stage = _needs_host_staging(labels, dist)
     ops, got = [], {}
     for peer, mine in ((rank - 1, labels[:radius]), (rank + 1, labels[-radius:])):
@@ -151,8 +149,17 @@ def _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi
         req.wait()
     up, down = got.get(rank - 1), got.get(rank + 1)
     extended = torch.cat([t.to(labels.device) for t in (up, labels, down) if t is not None])
-    del up, down, got
-    first = radius if rank > 0 else 0
+    return extended, (radius if rank > 0 else 0)
+
+
+def _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, radius):
+    """_intensity_of for the slab [lo, hi) of a sharded run.  The shell of a voxel depends on the labels within `radius` planes
+    of it only, so every rank takes `radius` planes of the final global labels from either neighbour
+    (_slab_with_neighbour_planes), expands the extended slab and keeps its own planes - exactly the planes [lo, hi) of the whole
+    volume's shell."""
+    if not radius:
+        return _intensity_of(eng, labels, raw_vol[lo:hi], N)
+    extended, first = _slab_with_neighbour_planes(labels, dist, rank, world, radius)
     raw_dev = hostio.upload(eng, raw_vol[lo - first:lo - first + int(extended.shape[0])], what="h2d_raw")
     try:
         part = eng.cc_intensity(labels, raw_dev[first:first + (hi - lo)], N)
@@ -174,7 +181,16 @@ def _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius=0):
         count_blobs.last_intensity["shell_radius"] = int(shell_radius)
 
 
-def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_vol=None, shell_radius=0):
+def _write_shape_table(path_out, brain, stats, N):
+    """<output_location>/cell_shape/<brain>.csv - in a sub-folder, for _write_intensity_table's reason"""
+    folder = os.path.join(path_out, "cell_shape")
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
+        fh.write(cell_shape_csv_text(stats, N))
+    count_blobs.last_shape = {"n": int(N)}
+
+
+def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_vol=None, shell_radius=0, shape=False):
     """One process per GPU: every rank labels a Z-slab of the mask, seams are merged (parallel.ccl_sharded) and every
     rank writes ITS label slab straight into the output .npy (rank 0 creates the file once N - and with it the label
     dtype - is known); only the merged statistics travel to rank 0.  No rank ever holds the whole label volume (17 GB for
@@ -183,6 +199,9 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
     statistics are taken on the filtered labels.  raw_vol: the raw volume (settings["mi355x"]["intensity_stats"]) - every
     rank measures planes [lo, hi) of it under its final global labels, rank 0 merges the parts into its stats.  shell_radius:
     settings["mi355x"]["background_shell"] - the shells around the cells are measured too (_intensity_and_shell_of_slab).
+    shape: settings["mi355x"]["shape_stats"] - every rank takes one plane of the final global labels from either neighbour slab
+    (a face of a voxel is exposed or not by its neighbour across the cut), measures its own planes of the extended slab with their
+    absolute z (HipEngine.cc_shape) and rank 0 adds the parts up (every slab holds a plane: count_blobs checked).
     Returns (N, stats | None)."""
     from .parallel import ccl_sharded, merge_stats
 
@@ -251,6 +270,26 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
             except Exception as exc:
                 failed = f"rank 0: {exc!r}"
         _raise_if_any_failed(dist, failed, "count_blobs: merging the intensity statistics")
+    if shape:
+        # (as for the intensity statistics: every outcome is exchanged before the next collective)
+        part, failed = None, None
+        try:
+            if labels is not None:
+                extended, first = _slab_with_neighbour_planes(labels, dist, rank, world, 1)
+                part = eng.cc_shape(extended, N, keep=(first, hi - lo), z_abs0=lo - first)
+                del extended
+        except Exception as exc:
+            failed = f"rank {rank}: {exc!r}"
+        _raise_if_any_failed(dist, failed, "count_blobs: the shape statistics")
+        parts = [None] * world
+        dist.gather_object(part, parts if rank == 0 else None, dst=0)
+        failed = None
+        if rank == 0:
+            try:
+                stats.update(finish_shape(merge_shape(parts), stats["voxel_counts"]))
+            except Exception as exc:
+                failed = f"rank 0: {exc!r}"
+        _raise_if_any_failed(dist, failed, "count_blobs: merging the shape statistics")
     out_path = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
     err = [None]
     if rank == 0:
@@ -318,13 +357,23 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     _sumsq / _min / _max / _mean, contrast (= intensity_mean / shell_mean; 0.0 for a cell without a shell) and shell_radius, the table
     the matching columns and ``count_blobs.last_intensity`` "shell_radius".  A cached pickle without these keys, or with another
     shell_radius, is completed.  Needs 4 (r = 1) or 8 more bytes of HBM per voxel; under torch.distributed every slab must hold at
-    least r planes.  Off, 0 or absent: nothing of this happens."""
+    least r planes.  Off, 0 or absent: nothing of this happens.
+
+    ``settings["mi355x"]["shape_stats"]`` true (on its own: no raw volume is opened): the shape of every cell is measured on the final
+    labels on the device - second-order moments of the voxel coordinates and the exposed faces per axis, exact integers.  The pickle
+    gains shape_sums / _moments / _faces / _surface_voxels and the derived shape_covariance, shape_axes (principal-axis variances),
+    shape_elongation and shape_sphericity (hostlogic.finish_shape), the table goes to <output_location>/cell_shape/<brain>.csv and
+    ``count_blobs.last_shape`` holds {"n"}.  Cached labels are measured too, and a cached pickle without the keys is rewritten with
+    them.  Needs no further volume in HBM; a mask that needs the slab-streamed path is refused; under torch.distributed every slab
+    must hold a plane.  Off or absent: nothing of this happens."""
     from .engine import shared_engine
 
     bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
     shell_radius = background_shell_radius(settings)  # (raises on a bad value, or without intensity_stats, before any file is touched)
     count_blobs.last_filter = None  # set by a run that filtered
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
+    count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
+    shape_on = shape_stats_enabled(settings)
     if bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
         print(f"min_size {min_size} / max_size {max_size} are ignored, as in the reference; "
               "settings['mi355x']['size_filter'] = true applies them")
@@ -343,6 +392,12 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         if thin:
             raise ValueError(f"count_blobs: settings['mi355x']['background_shell'] = {shell_radius} needs Z-slabs of at least {shell_radius} "
                              f"planes on every rank, {shape[0]} planes over {dist.get_world_size()} ranks give slabs of {min(thin)}")
+    if sharded and shape_on:
+        # (a face across a cut is judged from the neighbour slab's plane: the same check with a radius of 1)
+        thin = [hi - lo for lo, hi in _even_slabs(shape[0], dist.get_world_size()) if hi - lo < 1]
+        if thin:
+            raise ValueError(f"count_blobs: settings['mi355x']['shape_stats'] needs Z-slabs of at least 1 plane on every rank, "
+                             f"{shape[0]} planes over {dist.get_world_size()} ranks give slabs of {min(thin)}")
     raw_vol, raw_file = None, None
     if intensity_stats_enabled(settings):  # (before any file is written; under torch.distributed all ranks raise or none does)
         failed = None
@@ -377,7 +432,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
             raise RuntimeError(f"count_blobs: rank 0 failed while looking for a cached labelling: {branch[0][1]}")
         if not branch[0][1]:
             try:
-                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds, raw_vol, shell_radius)
+                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds, raw_vol, shell_radius, shape_on)
             finally:
                 if own:
                     eng.close()
@@ -390,6 +445,8 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
                         fh.write(cells_csv_bytes(stats, N))
                     if raw_vol is not None:
                         _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
+                    if shape_on:
+                        _write_shape_table(path_out, brain, stats, N)
                     end = datetime.datetime.now()
                     print(f"{end} {brain} {brain_i} / {len_b} Done ({dist.get_world_size()} ranks); Took {end - start}")
                 except Exception as exc:
@@ -410,12 +467,15 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     try:
         import time
 
-        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol, shell_radius)
+        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol, shell_radius,
+                                                       shape_on)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
         if raw_vol is not None:
             _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
+        if shape_on:
+            _write_shape_table(path_out, brain, stats, N)
         count_blobs.last_timings["csv_s"] = time.perf_counter() - t_csv
         t_join = time.perf_counter()
         if defer_write:
@@ -435,13 +495,14 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0):
+def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0, shape=False):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
     made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
     filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write.  raw_vol: the
     raw volume (settings["mi355x"]["intensity_stats"]), measured under the labels - fresh or cached - after cc_stats.
-    shell_radius: settings["mi355x"]["background_shell"] - the shells around the cells are measured with the same raw tensor."""
+    shell_radius: settings["mi355x"]["background_shell"] - the shells around the cells are measured with the same raw tensor.
+    shape: settings["mi355x"]["shape_stats"] - the shape accumulators are taken on the labels, fresh or cached, after that."""
     import time
 
     labels_dev = None
@@ -472,6 +533,10 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                               f"per voxel in HBM beside the mask, its labels and the raw volume "
                               f"({int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv) / 2**30:.1f} GiB), the HBM budget is "
                               f"{budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
+        if shape and not cached and need > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the mask and its labels in HBM "
+                              f"({need / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling "
+                              "does not measure; raise settings['mi355x']['hbm_budget_gb'] or switch shape_stats off")
         if not cached and need > budget:
             # the mask + its uint32 labels do not fit this GPU: Z-slabs through the device, seams merged on the host
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
@@ -559,7 +624,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             with open(path, "wb") as fh:
                 pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
 
-        have_intensity = have_shell = False
+        have_intensity = have_shell = have_shape = False
         if cached_stats:
             print(f"Found stats at {cached_stats}")
             with open(cached_stats, "rb") as fh:
@@ -567,9 +632,15 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             have_intensity = all(k in stats for k in _INTENSITY_STATS_KEYS)
             # (complete only with every shell key and the radius asked for)
             have_shell = all(k in stats for k in _SHELL_STATS_KEYS) and stats["shell_radius"] == shell_radius
+            have_shape = all(k in stats for k in SHAPE_KEYS)
         measure_cells = raw_vol is not None and not have_intensity
         measure_shell = raw_vol is not None and shell_radius > 0 and not have_shell
         measure = measure_cells or measure_shell
+        measure_shape = shape and not have_shape
+        if measure_shape and labels_dev is None and int(labels.size) * 4 > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the cached labels in HBM "
+                              f"({int(labels.size) * 4 / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
+                              "settings['mi355x']['hbm_budget_gb'] or switch shape_stats off")
         if measure and labels_dev is None and int(labels.size) * (4 + 2) > budget:
             raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_stats'] needs the cached labels and the raw volume "
                               f"in HBM ({int(labels.size) * 6 / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
@@ -588,7 +659,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                 if labels_dev is None:
                     labels_dev = cached_labels_to_device()
                 stats = eng.cc_stats(labels_dev, N)
-            if not measure:
+            if not measure and not measure_shape:
                 write_stats(os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("stats")
         if measure:
@@ -601,8 +672,15 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                 stats.update(finish_shell(*shell_part, stats["intensity_mean"]))
                 stats["shell_radius"] = int(shell_radius)
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
-            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
+            if not measure_shape:
+                write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")
+        if measure_shape:
+            if labels_dev is None:
+                labels_dev = cached_labels_to_device()
+            stats.update(finish_shape(eng.cc_shape(labels_dev, N), stats["voxel_counts"]))
+            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
+            mark("shape")
     except BaseException:
         try:
             wait()  # (do not leave the writer thread behind an error of this one)

@@ -733,6 +733,37 @@ class HipEngine:
         self._leave()  # (torch's stream now waits for the sweeps: the scratch volume freed here is not reused before them)
         return shell
 
+    def cc_shape(self, labels, n: int, keep=None, z_abs0: int = 0) -> dict:
+        """Per-label shape accumulators of a label volume (dlv_cc_shape_dev).  labels: int32 (uint32 payload) (Zb,Y,X) in HBM,
+        contiguous.  keep: (first, planes) - the planes of `labels` that are measured (default: all); the others only serve as
+        neighbours (a slab extended by its neighbours' planes).  z_abs0: the absolute z of the buffer's first plane.
+        -> {"shape_counts": uint32 (n+1), "shape_sums": uint64 (n+1,3) = sum z, y, x, "shape_moments": uint64 (n+1,6) = sum zz,
+        yy, xx, zy, zx, yx, "shape_faces": uint64 (n+1,3) = exposed faces per axis z, y, x, "shape_surface_voxels": uint32 (n+1)};
+        row 0 and a label without a measured voxel are all zero, so slabs add up (hostlogic.merge_shape)."""
+        torch = self.torch
+        if not isinstance(labels, torch.Tensor) or labels.device != self.device:
+            raise ValueError(f"cc_shape: labels: expected a torch tensor on {self.device}, got {type(labels).__name__} on "
+                             f"{getattr(labels, 'device', None)}")
+        if labels.dtype != torch.int32 or labels.dim() != 3:
+            raise ValueError(f"cc_shape: labels: expected a 3-D tensor of {torch.int32}, got {labels.dim()}-D {labels.dtype}")
+        if not labels.is_contiguous() or labels.numel() == 0:
+            raise ValueError(f"cc_shape: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
+        Z, Y, X = (int(v) for v in labels.shape)
+        first, planes = (0, Z) if keep is None else (int(keep[0]), int(keep[1]))
+        if first < 0 or planes < 1 or first + planes > Z:
+            raise ValueError(f"cc_shape: keep = {keep!r} does not select planes of the {Z} in the buffer")
+        n, z_abs0 = int(n), int(z_abs0)
+        if n < 0 or z_abs0 < 0:
+            raise ValueError(f"cc_shape: n = {n}, z_abs0 = {z_abs0}")
+        out = {"shape_counts": np.zeros(n + 1, dtype=np.uint32), "shape_sums": np.zeros((n + 1, 3), dtype=np.uint64),
+               "shape_moments": np.zeros((n + 1, 6), dtype=np.uint64), "shape_faces": np.zeros((n + 1, 3), dtype=np.uint64),
+               "shape_surface_voxels": np.zeros(n + 1, dtype=np.uint32)}
+        self._enter()
+        self._check(self.lib.dlv_cc_shape_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, first, planes, z_abs0, n,
+                                              *(a.ctypes.data_as(C.c_void_p) for a in out.values())))
+        self._leave()
+        return out
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

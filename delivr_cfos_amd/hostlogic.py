@@ -230,6 +230,122 @@ def cell_intensity_csv_text(stats: dict, n: int) -> str:
     return "\n".join(lines) + "\n"
 
 
+SHAPE_RAW_KEYS = ("shape_counts", "shape_sums", "shape_moments", "shape_faces", "shape_surface_voxels")  # what HipEngine.cc_shape returns
+SHAPE_KEYS = ("shape_sums", "shape_moments", "shape_faces", "shape_surface_voxels", "shape_covariance", "shape_axes",
+              "shape_elongation", "shape_sphericity")  # finish_shape's keys
+_SHAPE_RAW_LAYOUT = {"shape_counts": (np.uint32, ()), "shape_sums": (np.uint64, (3,)), "shape_moments": (np.uint64, (6,)),
+                     "shape_faces": (np.uint64, (3,)), "shape_surface_voxels": (np.uint32, ())}
+_MOMENT_AXES = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))  # zz, yy, xx, zy, zx, yx
+
+
+def shape_stats_enabled(settings) -> bool:
+    """count_blobs' per-cell shape statistics: on only for a truthy settings["mi355x"]["shape_stats"]."""
+    return bool(((settings or {}).get("mi355x") or {}).get("shape_stats"))
+
+
+def merge_shape(parts) -> dict:
+    """Per-slab dicts of HipEngine.cc_shape over the same labels 0..n -> the dict of the whole volume: every array adds (an absent
+    label is all zero).  None entries (empty slabs) are skipped; with nothing left, or rows that disagree, ValueError."""
+    parts = [p for p in parts if p is not None]
+    if not parts:
+        raise ValueError("merge_shape: no slab to merge")
+    rows = len(parts[0]["shape_counts"])
+    if any(np.shape(p[k]) != (rows,) + _SHAPE_RAW_LAYOUT[k][1] for p in parts for k in SHAPE_RAW_KEYS):
+        raise ValueError("merge_shape: the slabs do not cover the same labels")
+    out = {k: np.zeros((rows,) + tail, dtype=dt) for k, (dt, tail) in _SHAPE_RAW_LAYOUT.items()}
+    for p in parts:
+        for k, (dt, _) in _SHAPE_RAW_LAYOUT.items():
+            out[k] += np.asarray(p[k], dtype=dt)
+    return out
+
+
+def _shape_numerators(n: np.ndarray, S: np.ndarray, M: np.ndarray) -> np.ndarray:
+    """n * S_ab - S_a * S_b per label and moment as float64, each the exact integer rounded once.  The sums are shifted to the
+    origin o = floor(centroid) in wrapping uint64 arithmetic: S'_a = S_a - n o_a lies in [0, n), S'_aa = sum (a - o_a)^2 is below
+    2^64 and so exact, and the numerator does not depend on the origin.  While n * max S'_aa + n^2 stays below 2^62 - every real
+    cell - the wrapped numerator read as int64 is the true one (|S'_ab| <= max S'_aa by Cauchy-Schwarz); the other labels are
+    recomputed with Python integers."""
+    nn = np.where(n == 0, 1, n).astype(np.uint64)
+    o = S // nn[:, None]
+    Ss = S - nn[:, None] * o
+    num = np.empty(M.shape, dtype=np.float64)
+    diag_max = np.zeros(len(n), dtype=np.float64)
+    for j, (a, b) in enumerate(_MOMENT_AXES):
+        Ms = M[:, j] - o[:, a] * S[:, b] - o[:, b] * S[:, a] + nn * o[:, a] * o[:, b]
+        if a == b:
+            np.maximum(diag_max, Ms.astype(np.float64), out=diag_max)
+        num[:, j] = (nn * Ms - Ss[:, a] * Ss[:, b]).view(np.int64).astype(np.float64)
+    nf = nn.astype(np.float64)
+    for l in np.flatnonzero(nf * diag_max * (1 + 2.0**-50) + nf * nf >= 2.0**62).tolist():
+        k, s, m = int(n[l]), [int(v) for v in S[l]], [int(v) for v in M[l]]
+        num[l] = [float(k * m[j] - s[a] * s[b]) for j, (a, b) in enumerate(_MOMENT_AXES)]
+    num[n == 0] = 0.0
+    return num
+
+
+def finish_shape(merged: dict, voxel_counts) -> dict:
+    """The whole-volume accumulators (HipEngine.cc_shape / merge_shape) -> what count_blobs stores, N+1 rows each, row 0 all zero:
+    shape_sums, shape_moments, shape_faces uint64 and shape_surface_voxels uint32, the exact integers, and
+      shape_covariance  float64 (N+1, 6), order zz, yy, xx, zy, zx, yx: (n S_ab - S_a S_b) / n^2, plus 1/12 on zz, yy, xx - the
+                        covariance of the solid made of the cell's unit cubes (a single voxel is not degenerate).  The numerator
+                        is exact, converted to float64 once and divided once;
+      shape_axes        float64 (N+1, 3): the eigenvalues of that covariance, descending (np.linalg.eigvalsh), clipped below at 0;
+      shape_elongation  sqrt(axes[:, 0] / axes[:, 2]), at least 1, finite because of the 1/12;
+      shape_sphericity  pi^(1/3) (6 n)^(2/3) / (faces_z + faces_y + faces_x): the area is the DIGITAL face count, not a smooth
+                        surface estimate, so a cube of any size gives (pi/6)^(1/3) ~ 0.806 and a digital ball about 2/3.
+    A label without a voxel has zeros everywhere.  RuntimeError when the measured counts of the labels 1..N differ from
+    voxel_counts: labels and statistics do not belong together."""
+    counts = np.asarray(voxel_counts)
+    raw = {k: np.array(merged[k], dtype=dt) for k, (dt, _) in _SHAPE_RAW_LAYOUT.items()}
+    rows = len(raw["shape_counts"])
+    if len(counts) != rows or rows < 1 or any(raw[k].shape != (rows,) + tail for k, (_, tail) in _SHAPE_RAW_LAYOUT.items()):
+        raise RuntimeError(f"shape statistics of {rows} rows beside voxel counts of {len(counts)}")
+    bad = np.flatnonzero(raw["shape_counts"][1:] != counts[1:]) + 1
+    if len(bad):
+        l = int(bad[0])
+        raise RuntimeError(f"shape statistics and voxel counts disagree on {len(bad)} label(s), first label {l}: "
+                           f"{int(counts[l])} voxels counted, {int(raw['shape_counts'][l])} measured - labels and statistics of "
+                           "different brains?")
+    n = raw.pop("shape_counts").astype(np.uint64)
+    n[0] = 0
+    for a in raw.values():
+        a[0] = 0
+    present = n != 0
+    nf = np.where(present, n, 1).astype(np.float64)
+    cov = _shape_numerators(n, raw["shape_sums"], raw["shape_moments"]) / (nf * nf)[:, None]
+    cov[:, :3] += 1.0 / 12.0
+    cov[~present] = 0.0
+    mat = np.empty((rows, 3, 3), dtype=np.float64)
+    for j, (a, b) in enumerate(_MOMENT_AXES):
+        mat[:, a, b] = mat[:, b, a] = cov[:, j]
+    axes = np.maximum(np.linalg.eigvalsh(mat)[:, ::-1], 0.0)
+    elong = np.zeros(rows, dtype=np.float64)
+    np.sqrt(np.divide(axes[:, 0], axes[:, 2], out=elong, where=present), out=elong)
+    area = raw["shape_faces"].sum(axis=1).astype(np.float64)
+    spher = np.zeros(rows, dtype=np.float64)
+    np.divide(np.pi ** (1.0 / 3.0) * (6.0 * nf) ** (2.0 / 3.0), area, out=spher, where=present & (area > 0))
+    return {**raw, "shape_covariance": cov, "shape_axes": np.ascontiguousarray(axes), "shape_elongation": elong,
+            "shape_sphericity": spher}
+
+
+def cell_shape_csv_text(stats: dict, n: int) -> str:
+    """count_blobs' cell_shape/<brain>.csv: header ``Blob,Size,FacesZ,FacesY,FacesX,SurfaceVoxels,VarMajor,VarMid,VarMinor,
+    Elongation,Sphericity``, one row per label 1..N - all N, as cell_intensity_csv_text - integers written plainly, floats as
+    repr of the float64 value, every line ended by a newline."""
+    n = int(n)
+    ints = [np.asarray(stats["voxel_counts"])[1:n + 1].tolist()]
+    ints += [np.asarray(stats["shape_faces"])[1:n + 1, k].tolist() for k in range(3)]
+    ints.append(np.asarray(stats["shape_surface_voxels"])[1:n + 1].tolist())
+    floats = [np.asarray(stats["shape_axes"], dtype=np.float64)[1:n + 1, k].tolist() for k in range(3)]
+    floats += [np.asarray(stats[k], dtype=np.float64)[1:n + 1].tolist() for k in ("shape_elongation", "shape_sphericity")]
+    if any(len(c) != n for c in ints + floats):
+        raise ValueError("statistics shorter than the label count")
+    lines = ["Blob,Size,FacesZ,FacesY,FacesX,SurfaceVoxels,VarMajor,VarMid,VarMinor,Elongation,Sphericity"]
+    lines.extend(f"{i},{c},{fz},{fy},{fx},{sv},{a0!r},{a1!r},{a2!r},{el!r},{sp!r}"
+                 for i, (c, fz, fy, fx, sv, a0, a1, a2, el, sp) in enumerate(zip(*ints, *floats), 1))
+    return "\n".join(lines) + "\n"
+
+
 def pass_schedule(tta: bool) -> List[Tuple[Optional[int], int]]:
     """(flip_dim, repeat) per DISTINCT pass.  The reference runs 1 plain pass, then 4 x {noise,
     noise + flip Z (dim 2), noise + flip Y (dim 3)} (inference/inference.py:261-279); its noise is

@@ -318,6 +318,19 @@ int dlv_cc_intensity_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_
  * pointer (4 / 2 bytes) or labels_dev / shell_dev / scratch_dev overlapping: DLV_EINVAL. Asynchronous on the context's stream. */
 int dlv_cc_shell_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
                      int64_t raw_pitch_y, int64_t raw_pitch_z, int radius, uint32_t* shell_dev, uint32_t* scratch_dev);
+/* Per-label shape accumulators of a label volume (no counterpart in the reference): second-order moments of the voxel coordinates
+ * and the exposed faces. labels_dev: uint32 (Zb,Y,X) contiguous, labels 0..n. The voxels of the buffer's planes
+ * [z_first, z_first + nz) are measured, the other planes only serve as neighbours (the halo planes of a slab of a sharded run). The
+ * absolute z of buffer plane k is z_abs0 + k; y and x are the buffer's own. Host outputs of n+1 rows: counts uint32 (measured
+ * voxels), sums uint64 (n+1,3) = sum z, y, x, moments uint64 (n+1,6) = sum zz, yy, xx, zy, zx, yx (absolute coordinates), faces
+ * uint64 (n+1,3) = per axis z, y, x the pairs (measured voxel of label l, direction +-axis) whose face neighbour has a label != l or
+ * lies outside the buffer (z outside [0, Zb), or outside the Y / X range), surface_voxels uint32 = measured voxels with at least one
+ * such face. All exact. Row 0 (background) and a label without a measured voxel are all zero, so slabs merge by addition. Labels
+ * above n are not accumulated, and differ from every label as a neighbour. A NULL pointer, Zb/Y/X < 1, nz < 1, z_first < 0,
+ * z_first + nz > Zb, z_abs0 < 0, n >= 2^32 - 1 or labels not 4-byte aligned: DLV_EINVAL; z_abs0 + Zb, Y or X above 65536:
+ * DLV_EUNSUP (as dlv_cc_stats_dev). Synchronous. */
+int dlv_cc_shape_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Zb, int Y, int X, int z_first, int nz, int z_abs0, uint64_t n,
+                     uint32_t* counts, uint64_t* sums, uint64_t* moments, uint64_t* faces, uint32_t* surface_voxels);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

@@ -15,8 +15,8 @@ import numpy as np
 
 from . import hostio
 from .hostlogic import (INTENSITY_KEYS, SHAPE_KEYS, SHELL_KEYS, background_shell_radius, cell_intensity_csv_text, cell_shape_csv_text,
-                        cells_csv_bytes, csv_name, finish_intensity, finish_shape, finish_shell, intensity_stats_enabled, merge_intensity,
-                        merge_shape, merge_shell, shape_stats_enabled, size_filter_bounds)
+                        cells_csv_bytes, csv_name, finish_intensity, finish_shape, finish_shell, finish_split, intensity_stats_enabled,
+                        merge_intensity, merge_shape, merge_shell, shape_stats_enabled, size_filter_bounds, split_fused_settings)
 
 _INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
 _SHELL_STATS_KEYS = SHELL_KEYS + ("shell_radius",)  # ... and settings["mi355x"]["background_shell"]
@@ -86,6 +86,13 @@ def _note_filter(bounds, n_before: int, n_kept: int, voxels_removed: int, quiet:
     if not quiet:
         print(f"size filter (min_size {bounds[0]}, max_size {bounds[1]}): kept {n_kept} of {n_before} components, "
               f"removed {voxels_removed} voxels")
+
+
+def _note_split(split, n_before: int, n_after: int, components_split: int):
+    count_blobs.last_split = {"depth": int(split[0]), "min_core": int(split[1]), "n_before": int(n_before), "n_after": int(n_after),
+                              "components_split": int(components_split)}
+    print(f"split of fused cells (depth {split[0]}, min_core {split[1]}): {components_split} of {n_before} components split, "
+          f"{n_after} cells")
 
 
 def _open_raw_volume(settings, brain, shape):
@@ -365,7 +372,21 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     shape_elongation and shape_sphericity (hostlogic.finish_shape), the table goes to <output_location>/cell_shape/<brain>.csv and
     ``count_blobs.last_shape`` holds {"n"}.  Cached labels are measured too, and a cached pickle without the keys is rewritten with
     them.  Needs no further volume in HBM; a mask that needs the slab-streamed path is refused; under torch.distributed every slab
-    must hold a plane.  Off or absent: nothing of this happens."""
+    must hold a plane.  Off or absent: nothing of this happens.
+
+    ``settings["mi355x"]["split_fused"]`` = d (1..16; ``split_min_core`` = m, default 1): fused cells are split on the device right
+    after the labelling, before the size filter, so that min_size / max_size apply to the final cells.  The labels are eroded d
+    times with the 6 face neighbours (outside the volume counts as background); what is left are the cores, 26-connected, those of
+    fewer than m voxels dropped.  A component with two or more cores is divided among them - every voxel goes to the core nearest to
+    it in 26-steps through its own component, to the first core on a tie - and all cells are renumbered in raster order of their
+    first voxel (HipEngine.cc_split).  Everything written afterwards - label file, its name and dtype, statistics, CSV, the
+    intensity, shell and shape statistics - is what the split labels give; the pickle gains split_parent (the component a cell was
+    cut from, as the labelling numbered it), split_siblings (the cells that share that component and are still there after the size
+    filter; 1 for a cell that was not split) and split_depth, and ``count_blobs.last_split`` holds {"depth", "min_core", "n_before",
+    "n_after", "components_split"}.  A cached label file is reused as it is: it is NOT split again.  Needs 8 more bytes of HBM per
+    voxel while it runs; a mask that needs the slab-streamed path is refused.  Under torch.distributed the key is refused with
+    ValueError on every rank: the growth has no bounded reach, so a slab cannot be split on its own.  Off, 0 or absent: nothing of
+    this happens."""
     from .engine import shared_engine
 
     bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
@@ -373,6 +394,8 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     count_blobs.last_filter = None  # set by a run that filtered
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
+    count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
+    split = split_fused_settings(settings)  # (raises on a bad value before any file is touched)
     shape_on = shape_stats_enabled(settings)
     if bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
         print(f"min_size {min_size} / max_size {max_size} are ignored, as in the reference; "
@@ -386,6 +409,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     rank = dist.get_rank() if sharded else 0
 
     shape = tuple(int(v) for v in stack_shape[2:])
+    if sharded and split is not None:
+        # every rank reads the same settings: all raise, before any collective, or none does
+        raise ValueError(f"count_blobs: settings['mi355x']['split_fused'] = {split[0]} is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
+                         "its own; run step 3 on one device or switch split_fused off")
     if sharded and shell_radius:
         # every rank computes the same slabs: all raise, before any collective, or none does
         thin = [hi - lo for lo, hi in _even_slabs(shape[0], dist.get_world_size()) if hi - lo < shell_radius]
@@ -468,7 +496,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         import time
 
         N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol, shell_radius,
-                                                       shape_on)
+                                                       shape_on, split)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
@@ -495,14 +523,17 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0, shape=False):
+def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0, shape=False,
+                        split=None):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
     made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
     filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write.  raw_vol: the
     raw volume (settings["mi355x"]["intensity_stats"]), measured under the labels - fresh or cached - after cc_stats.
     shell_radius: settings["mi355x"]["background_shell"] - the shells around the cells are measured with the same raw tensor.
-    shape: settings["mi355x"]["shape_stats"] - the shape accumulators are taken on the labels, fresh or cached, after that."""
+    shape: settings["mi355x"]["shape_stats"] - the shape accumulators are taken on the labels, fresh or cached, after that.
+    split: settings["mi355x"]["split_fused"] (hostlogic.split_fused_settings) - a fresh labelling is split between dlv_ccl26_dev
+    and the size filter; its two scratch volumes are gone before the raw volume is uploaded, so the two peaks do not add."""
     import time
 
     labels_dev = None
@@ -537,6 +568,11 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the mask and its labels in HBM "
                               f"({need / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling "
                               "does not measure; raise settings['mi355x']['hbm_budget_gb'] or switch shape_stats off")
+        if split is not None and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 8) > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['split_fused'] = {split[0]} needs 8 more bytes per voxel in HBM "
+                              f"beside the mask and its labels ({int(bin_img.size) * (ccl_bytes_per_voxel() + 8) / 2**30:.1f} GiB), the HBM "
+                              f"budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling does not split; raise "
+                              "settings['mi355x']['hbm_budget_gb'] or switch split_fused off")
         if not cached and need > budget:
             # the mask + its uint32 labels do not fit this GPU: Z-slabs through the device, seams merged on the host
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
@@ -575,12 +611,20 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             labels_dev, N = eng.ccl26(mask_dev)
             del mask_dev
             mark("ccl26")
+            split_parent = None
+            if split is not None:
+                n_components = N
+                N, split_parent, components_split = eng.cc_split(labels_dev, N, split[0], split[1])
+                _note_split(split, n_components, N, components_split)
+                mark("split")
             if _filter_active(bounds):
                 n_before = N
                 counts_dev = eng.cc_counts(labels_dev, N)
                 N = eng.cc_size_filter(labels_dev, N, bounds[0], bounds[1], counts=counts_dev)
                 counts = counts_dev.cpu().numpy().view(np.uint32).astype(np.uint64)
                 _note_filter(bounds, n_before, N, int(counts[1:][~_keep_mask(counts, bounds)[1:]].sum()))
+                if split_parent is not None:  # (the rows of the cells the filter kept, in their order)
+                    split_parent = np.concatenate([split_parent[:1], split_parent[1:][_keep_mask(counts, bounds)[1:]]])
                 del counts_dev
                 mark("size_filter")
             final = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
@@ -606,6 +650,9 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             print(f"Cached brain found at {cached} with {N} components, loading...")
             if _filter_active(bounds):
                 print(f"size filter: the cached labelling is reused as it is, min_size {bounds[0]} / max_size {bounds[1]} are not applied to it")
+            if split is not None:
+                print(f"split of fused cells: the cached labelling is reused as it is, it is not split (depth {split[0]}) again")
+            split_parent = None
             labels = np.load(cached, mmap_mode="r")
         mid = datetime.datetime.now()
         print(f"{mid} labelling+writing/loading took {mid - start} : {N}")
@@ -659,6 +706,9 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                 if labels_dev is None:
                     labels_dev = cached_labels_to_device()
                 stats = eng.cc_stats(labels_dev, N)
+            if split_parent is not None:
+                stats.update(finish_split(split_parent, count_blobs.last_split["n_before"]))
+                stats["split_depth"] = int(split[0])
             if not measure and not measure_shape:
                 write_stats(os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("stats")

@@ -446,6 +446,18 @@ __global__ void __launch_bounds__(256) ccl_relabel_lines_kernel(const unsigned s
         }
 }
 
+// The bit mask of a volume that is labelled already (bit k of word c: voxel 16 c + k holds a label): what ccl_init_kernel makes
+// of the byte mask, for dlv_ccl_number_forest
+__global__ void __launch_bounds__(256) ccl_bits_of_labels_kernel(const u32* __restrict__ fg, u64 n, unsigned short* __restrict__ bm) {
+    const u64 nch = (n + 15) / 16;
+    for (u64 c = (u64)blockIdx.x * blockDim.x + threadIdx.x; c < nch; c += (u64)gridDim.x * blockDim.x) {
+        unsigned bits = 0;
+        for (int k = 0; k < 16; ++k)
+            if (c * 16 + k < n && fg[c * 16 + k] != 0u) bits |= 1u << k;
+        bm[c] = (unsigned short)bits;
+    }
+}
+
 // ---- statistics -------------------------------------------------------------------------------------
 // per label: count, sum z/y/x (u64), bbox min/max (u32).  Contributions are aggregated before they reach memory:
 // each thread folds the runs of equal labels inside its 8 consecutive x voxels, then the lanes of a wave that hold
@@ -751,7 +763,81 @@ struct StatsRaw {
     const u64* sums() const { return (const u64*)(host.data() + off_sum); }
 };
 
+// The scratch of a labelling of n voxels (slot WS_CCL): root counts per renumbering block, their group sums, the two bit masks
+// (foreground, roots), the chunk list - 0.5 B per voxel.  The union-find's parent array IS the label volume
+// (ccl_assign_roots_kernel)
+struct CclWs {
+    u32 *counts, *gsum, *list_n, *list;
+    unsigned short *bm, *rb;  // bit mask of the volume (ccl_init_kernel), root bits (written for every chunk by ccl_assign_roots_kernel)
+    u64 nb, nch;
+};
+int ccl_ws_get(dlv_ctx* ctx, u64 n, CclWs& w) {
+    w.nb = (n + RCHUNK - 1) / RCHUNK;
+    w.nch = (n + 15) / 16;
+    char* ws;
+    const size_t counts_off = 0;
+    const size_t gsum_off = (counts_off + (size_t)(w.nb + 1) * 4 + 255) & ~(size_t)255;
+    const size_t bm_off = (gsum_off + (size_t)((w.nb + SGRP - 1) / SGRP + 1) * 4 + 255) & ~(size_t)255;
+    const size_t rb_off = (bm_off + (size_t)(w.nch + 4) * 2 + 255) & ~(size_t)255;
+    const size_t list_off = (rb_off + (size_t)(w.nch + 4) * 2 + 255) & ~(size_t)255;  // [list_n, pad, list[nch]]
+    DLV_TRY(dlv_ws_get(ctx, WS_CCL, list_off + 256 + (size_t)w.nch * 4 + 256, (void**)&ws));
+    w.list_n = (u32*)(ws + list_off);
+    w.list = (u32*)(ws + list_off + 256);
+    w.rb = (unsigned short*)(ws + rb_off);
+    w.counts = (u32*)(ws + counts_off);
+    w.gsum = (u32*)(ws + gsum_off);
+    w.bm = (unsigned short*)(ws + bm_off);
+    return DLV_OK;
+}
+
+// The roots of the forest in `labels` (an entry that holds its own index, among the voxels of w.bm) get the labels 1..N in raster
+// order, w.rb records which entries they are, w.counts[w.nb] receives N: the renumbering of dlv_ccl26_dev, and of
+// dlv_ccl_number_forest.  The other entries still hold their root's index when this returns.
+int ccl_number_roots(dlv_ctx* ctx, const CclWs& w, u32* labels, u64 n) {
+    hipLaunchKernelGGL(ccl_count_roots_kernel, dim3((unsigned)w.nb), dim3(256), 0, ctx->stream, w.bm, labels, n, w.counts);
+    DLV_LAUNCH_CHECK(ctx, "ccl_count_roots_kernel");
+    const u64 ng = (w.nb + SGRP - 1) / SGRP;
+    hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, w.counts, w.nb, w.gsum);
+    hipLaunchKernelGGL(ccl_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, w.gsum, ng, w.counts + w.nb);
+    hipLaunchKernelGGL(ccl_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, w.counts, w.nb, w.gsum);
+    DLV_LAUNCH_CHECK(ctx, "ccl_scan_counts_kernel");
+    hipLaunchKernelGGL(ccl_assign_roots_kernel, dim3((unsigned)w.nb), dim3(256), 0, ctx->stream, w.bm, labels, n, w.counts, labels, w.rb);
+    DLV_LAUNCH_CHECK(ctx, "ccl_assign_roots_kernel");
+    return DLV_OK;
+}
+
+// every voxel of the volume is written: 0 for the background, the root's label for the rest
+int ccl_relabel_whole(dlv_ctx* ctx, const CclWs& w, u32* labels, u64 n, bool aligned) {
+    if (aligned)
+        hipLaunchKernelGGL(ccl_relabel_lines_kernel, dim3((unsigned)std::min<u64>((n / 1024 + 3) / 4 + 1, (u64)256 * 32)), dim3(256), 0,
+                           ctx->stream, w.bm, w.rb, n, labels);
+    else
+        hipLaunchKernelGGL(ccl_relabel_kernel, dim3((unsigned)std::min<u64>((w.nch + 255) / 256, (u64)256 * 64)), dim3(256), 0, ctx->stream,
+                           w.bm, w.rb, n, labels, aligned);
+    DLV_LAUNCH_CHECK(ctx, "ccl_relabel_kernel");
+    return DLV_OK;
+}
+
 }  // namespace
+
+// common.h: the renumbering half of dlv_ccl26_dev for a forest that somebody else has built
+int dlv_ccl_number_forest(dlv_ctx* ctx, const uint32_t* fg_dev, uint32_t* forest_dev, uint64_t n, uint64_t* n_out) {
+    if (!ctx || !fg_dev || !forest_dev || !n_out || n == 0) return DLV_EINVAL;
+    if (n > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "volumes above 2^32 voxels need 64-bit labels");
+    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    CclWs w;
+    DLV_TRY(ccl_ws_get(ctx, n, w));
+    const int gs = (int)std::min<u64>((w.nch + 255) / 256, (u64)256 * 64);
+    hipLaunchKernelGGL(ccl_bits_of_labels_kernel, dim3(gs), dim3(256), 0, ctx->stream, fg_dev, (u64)n, w.bm);
+    DLV_LAUNCH_CHECK(ctx, "ccl_bits_of_labels_kernel");
+    DLV_TRY(ccl_number_roots(ctx, w, forest_dev, n));
+    DLV_TRY(ccl_relabel_whole(ctx, w, forest_dev, n, (reinterpret_cast<uintptr_t>(forest_dev) & 15) == 0));
+    u32 total = 0;
+    DLV_HIP(ctx, hipMemcpyAsync(&total, w.counts + w.nb, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_out = total;
+    return DLV_OK;
+}
 
 extern "C" {
 
@@ -761,63 +847,37 @@ int dlv_ccl26_dev(dlv_ctx* ctx, const uint8_t* mask_dev, int Z, int Y, int X, ui
     const u64 n = (u64)Z * Y * X;
     if (n > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "volumes above 2^32 voxels need 64-bit labels");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
-    const u64 nb = (n + RCHUNK - 1) / RCHUNK;
-    char* ws;
-    const u64 nch = (n + 15) / 16;
-    // scratch: root counts per renumbering block, their group sums, the two bit masks (foreground, roots), the chunk list - 0.5 B per
-    // voxel.  The union-find's parent array IS the label volume (ccl_assign_roots_kernel)
-    const size_t counts_off = 0;
-    const size_t gsum_off = (counts_off + (size_t)(nb + 1) * 4 + 255) & ~(size_t)255;
-    const size_t bm_off = (gsum_off + (size_t)((nb + SGRP - 1) / SGRP + 1) * 4 + 255) & ~(size_t)255;
-    const size_t rb_off = (bm_off + (size_t)(nch + 4) * 2 + 255) & ~(size_t)255;
-    const size_t list_off = (rb_off + (size_t)(nch + 4) * 2 + 255) & ~(size_t)255;  // [list_n, pad, list[nch]]
-    DLV_TRY(dlv_ws_get(ctx, WS_CCL, list_off + 256 + (size_t)nch * 4 + 256, (void**)&ws));
-    u32* list_n = (u32*)(ws + list_off);
-    u32* list = (u32*)(ws + list_off + 256);
+    CclWs w;
+    DLV_TRY(ccl_ws_get(ctx, n, w));
     u32* L = labels_dev;
-    unsigned short* rb = (unsigned short*)(ws + rb_off);  // root bits, one word per 16 voxels (written for every chunk by ccl_assign_roots_kernel)
-    u32* counts = (u32*)(ws + counts_off);
-    u32* gsum = (u32*)(ws + gsum_off);
-    unsigned short* bm = (unsigned short*)(ws + bm_off);  // bit mask of the volume, one word per 16 voxels (ccl_init_kernel)
-    const int gs = (int)std::min<u64>((nch + 255) / 256, (u64)256 * 64);
+    const int gs = (int)std::min<u64>((w.nch + 255) / 256, (u64)256 * 64);
     // 16-byte accesses need the mask 16-byte and the labels 16-byte aligned (hipMalloc / torch allocations are)
     const bool aligned = ((reinterpret_cast<uintptr_t>(mask_dev) | reinterpret_cast<uintptr_t>(labels_dev)) & 15) == 0;
     // bytes: the byte mask is read once (1 B), its bit mask written once and scanned by five kernels (6/8 B), the labels are
     // written once (4 B)
     DlvProf pr(ctx, "ccl26", 0.0, (double)n * (1 + 0.75 + 4));
     const bool simple = ctx->ccl_simple;  // A/B (dlv_diag_set): whole-volume relabel stores instead of memset + list
-    DLV_HIP(ctx, hipMemsetAsync(list_n, 0, 4, ctx->stream));
+    DLV_HIP(ctx, hipMemsetAsync(w.list_n, 0, 4, ctx->stream));
     if (!simple) DLV_HIP(ctx, hipMemsetAsync(labels_dev, 0, (size_t)n * 4, ctx->stream));
-    hipLaunchKernelGGL(ccl_init_kernel, dim3(gs), dim3(256), 0, ctx->stream, mask_dev, L, n, aligned, bm, list, list_n);
+    hipLaunchKernelGGL(ccl_init_kernel, dim3(gs), dim3(256), 0, ctx->stream, mask_dev, L, n, aligned, w.bm, w.list, w.list_n);
     DLV_LAUNCH_CHECK(ctx, "ccl_init_kernel");
     const int gl = 256 * 16;  // list kernels: grid-stride over the device-side count
     if (aligned && X % 16 == 0)
-        hipLaunchKernelGGL(ccl_merge_list_kernel<true>, dim3(gl), dim3(256), 0, ctx->stream, bm, L, Y, X, list, list_n);
+        hipLaunchKernelGGL(ccl_merge_list_kernel<true>, dim3(gl), dim3(256), 0, ctx->stream, w.bm, L, Y, X, w.list, w.list_n);
     else
-        hipLaunchKernelGGL(ccl_merge_list_kernel<false>, dim3(gl), dim3(256), 0, ctx->stream, bm, L, Y, X, list, list_n);
+        hipLaunchKernelGGL(ccl_merge_list_kernel<false>, dim3(gl), dim3(256), 0, ctx->stream, w.bm, L, Y, X, w.list, w.list_n);
     DLV_LAUNCH_CHECK(ctx, "ccl_merge_kernel");
-    hipLaunchKernelGGL(ccl_compress_kernel, dim3(gl), dim3(256), 0, ctx->stream, bm, L, list, list_n);
+    hipLaunchKernelGGL(ccl_compress_kernel, dim3(gl), dim3(256), 0, ctx->stream, w.bm, L, w.list, w.list_n);
     DLV_LAUNCH_CHECK(ctx, "ccl_compress_kernel");
-    hipLaunchKernelGGL(ccl_count_roots_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, bm, L, n, counts);
-    DLV_LAUNCH_CHECK(ctx, "ccl_count_roots_kernel");
-    const u64 ng = (nb + SGRP - 1) / SGRP;
-    hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, counts, nb, gsum);
-    hipLaunchKernelGGL(ccl_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, gsum, ng, counts + nb);
-    hipLaunchKernelGGL(ccl_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, counts, nb, gsum);
-    DLV_LAUNCH_CHECK(ctx, "ccl_scan_counts_kernel");
-    hipLaunchKernelGGL(ccl_assign_roots_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, bm, L, n, counts, labels_dev, rb);
-    DLV_LAUNCH_CHECK(ctx, "ccl_assign_roots_kernel");
+    DLV_TRY(ccl_number_roots(ctx, w, labels_dev, n));
     if (!simple)
-        hipLaunchKernelGGL(ccl_relabel_list_kernel, dim3(gl), dim3(256), 0, ctx->stream, bm, rb, n, labels_dev, list, list_n, aligned);
-    else if (aligned)
-        hipLaunchKernelGGL(ccl_relabel_lines_kernel, dim3((unsigned)std::min<u64>((n / 1024 + 3) / 4 + 1, (u64)256 * 32)), dim3(256), 0,
-                           ctx->stream, bm, rb, n, labels_dev);
+        hipLaunchKernelGGL(ccl_relabel_list_kernel, dim3(gl), dim3(256), 0, ctx->stream, w.bm, w.rb, n, labels_dev, w.list, w.list_n, aligned);
     else
-        hipLaunchKernelGGL(ccl_relabel_kernel, dim3(gs), dim3(256), 0, ctx->stream, bm, rb, n, labels_dev, aligned);
+        DLV_TRY(ccl_relabel_whole(ctx, w, labels_dev, n, aligned));
     DLV_LAUNCH_CHECK(ctx, "ccl_relabel_kernel");
     pr.end();
     u32 total = 0;
-    DLV_HIP(ctx, hipMemcpyAsync(&total, counts + nb, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DLV_HIP(ctx, hipMemcpyAsync(&total, w.counts + w.nb, 4, hipMemcpyDeviceToHost, ctx->stream));
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = total;
     return DLV_OK;

@@ -264,6 +264,11 @@ int dlv_unet_apply_conv_shifts(dlv_ctx* ctx, const int* shifts);
 int dlv_range_step(dlv_ctx* ctx, int layer, const float* peaks, int* n_changed, const int* force_next /* or nullptr */);
 int dlv_range_plan(dlv_ctx* ctx, int layer, const float* peaks, int* nxt, bool* blind);
 size_t dlv_bf16_pack_bytes(const int features[6]);
+// ccl.hip: the renumbering half of dlv_ccl26_dev for a forest somebody else has built (cc_split.hip: the pieces).  Where
+// fg_dev[i] != 0, forest_dev[i] holds the linear index of the first voxel (in raster order) of i's tree, that voxel its own index.
+// forest_dev becomes the label volume: 1..N in the raster order of those first voxels, 0 where fg_dev is 0.  fg_dev is not
+// modified and must not be forest_dev; n <= 2^32 voxels; uses the labelling's scratch slot.  Synchronous (*n_out = N).
+int dlv_ccl_number_forest(dlv_ctx* ctx, const uint32_t* fg_dev, uint32_t* forest_dev, uint64_t n, uint64_t* n_out);
 #if defined(__HIPCC__)
 // Sum of a value over the 32 lanes of each wave half (lanes 0-31, lanes 32-63) with DPP adds only (five VALU
 // instructions, no LDS permute): the total is valid in lanes 16-31 resp. 48-63 - read it from lane 31 / 63.

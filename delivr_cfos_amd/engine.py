@@ -764,6 +764,52 @@ class HipEngine:
         self._leave()
         return out
 
+    def cc_split(self, labels, n: int, depth: int, min_core: int = 1):
+        """Fused cells split by their erosion cores, in place (dlv_cc_split_dev).  labels: int32 (uint32 payload) (Z,Y,X) in HBM,
+        contiguous, labels 0..n.  The labels are eroded `depth` (1..16) times with the 6 face neighbours; what is left are the
+        cores (26-connected; those of fewer than `min_core` voxels are dropped).  A label with two or more cores is divided among
+        them: every voxel goes to the core nearest to it in 26-steps through its own label, to the smallest core label on a tie.
+        The pieces and the labels that stay whole are renumbered 1..K in raster order of their first voxel, as ccl26 numbers.
+        -> (K, parent: uint32 ndarray of K+1 with parent[j] = the old label of piece j and parent[0] = 0, the number of labels
+        that were split).  Needs two more volumes of the labels' size while it runs."""
+        torch = self.torch
+        if not isinstance(labels, torch.Tensor) or labels.device != self.device:
+            raise ValueError(f"cc_split: labels: expected a torch tensor on {self.device}, got {type(labels).__name__} on "
+                             f"{getattr(labels, 'device', None)}")
+        if labels.dtype != torch.int32 or labels.dim() != 3:
+            raise ValueError(f"cc_split: labels: expected a 3-D tensor of {torch.int32}, got {labels.dim()}-D {labels.dtype}")
+        if not labels.is_contiguous() or labels.numel() == 0:
+            raise ValueError(f"cc_split: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
+        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= 16:
+            raise ValueError(f"cc_split: depth = {depth!r}: expected an integer 1..16")
+        if isinstance(min_core, bool) or not isinstance(min_core, (int, np.integer)) or int(min_core) < 1:
+            raise ValueError(f"cc_split: min_core = {min_core!r}: expected an integer >= 1")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"cc_split: n = {n}")
+        Z, Y, X = (int(v) for v in labels.shape)
+        work_a = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
+        work_b = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
+        k, n_split = C.c_uint64(), C.c_uint64()
+        cap = 2 * n + 2
+        self._enter()
+        try:
+            for attempt in (0, 1):
+                parent = torch.empty(cap, dtype=torch.int32, device=self.device)
+                k.value = 0
+                rc = self.lib.dlv_cc_split_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n, int(depth), int(min_core),
+                                               C.c_void_p(work_a.data_ptr()), C.c_void_p(work_b.data_ptr()), C.byref(k), C.byref(n_split),
+                                               C.c_void_p(parent.data_ptr()), cap)
+                if rc != 0 and attempt == 0 and int(k.value) + 1 > cap:  # (the table was too small: K is known now, the labels untouched)
+                    cap = int(k.value) + 1
+                    continue
+                self._check(rc)
+                break
+        finally:
+            self._leave()
+        K = int(k.value)
+        return K, parent[:K + 1].cpu().numpy().view(np.uint32), int(n_split.value)
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

@@ -205,6 +205,56 @@ def finish_shell(parts: dict, shell_counts, intensity_mean) -> dict:
             "shell_mean": mean, "contrast": contrast}
 
 
+SPLIT_KEYS = ("split_parent", "split_siblings")  # finish_split's keys
+SPLIT_MAX_DEPTH = 16  # dlv_cc_split_dev's largest depth
+
+
+def _is_integral(value) -> bool:
+    """an int, a numpy integer or a float with an integral value - never a bool"""
+    if isinstance(value, bool):
+        return False
+    if isinstance(value, (int, np.integer)):
+        return True
+    return isinstance(value, (float, np.floating)) and np.isfinite(value) and float(value) == int(value)
+
+
+def split_fused_settings(settings):
+    """count_blobs' split of fused cells: None when settings["mi355x"]["split_fused"] is absent, false or 0, else
+    (depth, min_core): the erosion depth, an integer 1..16, and settings["mi355x"]["split_min_core"], the smallest core in voxels,
+    an integer >= 1 (default 1).  ValueError for anything else (true, a float that is not integral, a string, a value outside the
+    range) and for split_min_core without split_fused."""
+    mi = (settings or {}).get("mi355x") or {}
+    value, min_core = mi.get("split_fused"), mi.get("split_min_core")
+    off = value is None or value is False or (_is_integral(value) and int(value) == 0)
+    if not off and (not _is_integral(value) or not 1 <= int(value) <= SPLIT_MAX_DEPTH):
+        raise ValueError(f"settings['mi355x']['split_fused'] = {value!r}: expected an erosion depth in voxels, an integer "
+                         f"1..{SPLIT_MAX_DEPTH} (0 / false: off)")
+    if min_core is not None and (not _is_integral(min_core) or int(min_core) < 1):
+        raise ValueError(f"settings['mi355x']['split_min_core'] = {min_core!r}: expected the smallest core in voxels, an integer >= 1")
+    if off:
+        if min_core is not None:
+            raise ValueError(f"settings['mi355x']['split_min_core'] = {min_core!r} needs settings['mi355x']['split_fused']: it is the "
+                             "smallest core the split counts")
+        return None
+    return int(value), 1 if min_core is None else int(min_core)
+
+
+def finish_split(parent, n_before: int) -> dict:
+    """HipEngine.cc_split's parent table (K+1 rows: parent[j] = the label piece j was cut from, 1..n_before; parent[0] = 0) -> what
+    count_blobs stores, K+1 rows each, row 0 zero: split_parent uint32 and split_siblings uint32 = the number of pieces with the
+    same parent (1 for a cell that was not split).  ValueError for a table without row 0 or with a parent outside 1..n_before."""
+    parent = np.array(parent, dtype=np.uint32).reshape(-1)
+    n_before = int(n_before)
+    if len(parent) < 1 or parent[0] != 0:
+        raise ValueError("finish_split: the parent table needs a row 0 that is 0")
+    if len(parent) > 1 and (int(parent[1:].min()) < 1 or int(parent[1:].max()) > n_before):
+        raise ValueError(f"finish_split: a parent outside 1..{n_before}")
+    pieces = np.bincount(parent[1:], minlength=n_before + 1)
+    siblings = pieces[parent].astype(np.uint32)
+    siblings[0] = 0
+    return {"split_parent": parent, "split_siblings": siblings}
+
+
 def cell_intensity_csv_text(stats: dict, n: int) -> str:
     """count_blobs' cell_intensity/<brain>.csv: header ``Blob,Size,Min,Max,Sum,SumSq,Mean``, one row per label 1..N - all N:
     this table has no reference to mirror, so none of its quirks (cells_csv_text drops the last label) - integers written

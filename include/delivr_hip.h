@@ -331,6 +331,27 @@ int dlv_cc_shell_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* r
  * DLV_EUNSUP (as dlv_cc_stats_dev). Synchronous. */
 int dlv_cc_shape_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Zb, int Y, int X, int z_first, int nz, int z_abs0, uint64_t n,
                      uint32_t* counts, uint64_t* sums, uint64_t* moments, uint64_t* faces, uint32_t* surface_voxels);
+/* Fused cells split by their erosion cores (no counterpart in the reference). labels_dev: uint32 (Z,Y,X) contiguous, labels 0..n,
+ * rewritten in place. (1) Cores: C_0 = labels != 0; C_{k+1}(v) = C_k(v) and C_k(u) for the 6 face neighbours u of v, a neighbour
+ * outside the volume counting as background; C = C_depth. (2) The cores are labelled 1..M as dlv_ccl26_dev labels a mask; with
+ * min_core > 1 the cores of fewer than min_core voxels are dropped as dlv_cc_size_filter_dev(min_size = min_core) drops them. A core
+ * lies in one label; cores(l) = the number of cores in label l. (3) Growth: G_0 = the core labels; G_{k+1}(v) = G_k(v) where that is
+ * not 0, else where labels(v) != 0 the smallest non-zero G_k(u) over the 26 neighbours u inside the volume with labels(u) ==
+ * labels(v) (0 without one), every step from G_k alone, up to the fixed point G: a voxel goes to the core nearest to it in 26-steps
+ * through its own label, to the smallest core label on a tie. (4) Pieces: key(v) = 0 where labels(v) == 0, G(v) where
+ * cores(labels(v)) >= 2 and G(v) != 0, M + labels(v) otherwise (a label with fewer than two cores stays whole). The distinct keys
+ * are numbered 1..K in C-raster order of their first voxel - dlv_ccl26_dev's numbering - and written to labels_dev: the foreground
+ * is unchanged, K >= the number of labels present, and a volume numbered by first voxel with nothing to split comes back as it was.
+ * Integer work only: exact and independent of scheduling.
+ * work_a_dev, work_b_dev: two scratch volumes of Z*Y*X uint32. *n_out = K; *n_split_out = the labels with two or more cores;
+ * parent_dev: parent_cap uint32 on the device, parent[j] = the old label of piece j for j = 1..K, parent[0] = 0.
+ * DLV_EINVAL with labels_dev unchanged for: parent_cap < K + 1 (*n_out is set to K: call again with a larger table), a NULL
+ * pointer, Z/Y/X < 1, depth outside 1..16, min_core < 1, a pointer that is not 4-byte aligned, volumes that overlap, a label above
+ * n in the volume, M + n beyond the uint32 keys, or a volume beyond the launch grid (as dlv_cc_shell_dev); above 2^32 voxels
+ * DLV_EUNSUP (as dlv_ccl26_dev). Synchronous. */
+int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int depth, int64_t min_core,
+                     uint32_t* work_a_dev, uint32_t* work_b_dev, uint64_t* n_out, uint64_t* n_split_out,
+                     uint32_t* parent_dev, uint64_t parent_cap);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

@@ -11,87 +11,67 @@
 // Measured once on an MI355X (profiles/README.md, "cc_shape"): 512^3 labels, 1.48 ms on a 1 % mask of small cells and 37.8 ms on a
 // 50 % random mask (one giant component: bound by the atomics on its row), 0.46 and 0.78 of cc_stats_kernel on the same labels.
 #include "common.h"
+#include "cc_fold.h"
 
 #include <algorithm>
 
 namespace {
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int IPT = 8;                // voxels per thread and sweep: two quads of one row
-constexpr u32 OUTSIDE = 0xffffffffu;  // "no voxel here": differs from every label 0..n (n < 2^32 - 1)
-
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int o) {
-    const u32 lo = __shfl_xor((u32)v, o, 64), hi = __shfl_xor((u32)(v >> 32), o, 64);
-    return ((u64)hi << 32) | lo;
-}
-
-// the thread's two quads of one row: 16-byte loads where the row starts on a 16-byte boundary and the quad lies inside it,
-// element by element elsewhere; OUTSIDE past the end of the row and for a row outside the buffer (exists == false)
-__device__ __forceinline__ void load_quads(const u32* __restrict__ row, bool exists, const u32 (&xq)[2], u32 X, u32 (&v)[IPT]) {
-    const bool vec = exists && (reinterpret_cast<uintptr_t>(row) & 15) == 0;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        if (vec && xq[q] + 4u <= X) {
-            const u32x4_t u = *reinterpret_cast<const u32x4_t*>(row + xq[q]);
-            v[4 * q] = u.x; v[4 * q + 1] = u.y; v[4 * q + 2] = u.z; v[4 * q + 3] = u.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[4 * q + j] = (exists && xq[q] + j < X) ? row[xq[q] + j] : OUTSIDE;
-        }
+// a (thread's, then a wave's) voxels under one label: z and y are the row's, so only x is summed here
+struct ShapeAcc {
+    u32 c_sv;   // count | surface voxels << 16  (<= 512 per wave: 16 bits each)
+    u32 fz_fy;  // exposed faces along z | along y << 16  (<= 1024 per wave and axis)
+    u32 fx;
+    u32 sx;     // (<= 512 * 65535 per wave: fits 32 bits)
+    u64 sxx;
+    static __device__ __forceinline__ ShapeAcc none() { return {0u, 0u, 0u, 0u, 0ull}; }
+    __device__ __forceinline__ void combine(int o) {
+        xor_add(c_sv, o); xor_add(fz_fy, o); xor_add(fx, o);
+        xor_add(sx, o); xor_add(sxx, o);
     }
-}
+};
 
-// cc_intensity_kernel's structure: a workgroup walks whole rows (z, y) of the measured planes [z_first, z_first + nz) of the
-// buffer; per sweep of T threads a thread takes voxels [4t, 4t+4) and [4(T+t), 4(T+t)+4) of the sweep's 8T voxels.  A wave
-// whose 512 voxels hold no label 1..n stops there.  One that holds a label reads the rows (z-1, y), (z+1, y), (z, y-1) and
-// (z, y+1) at the same x - a row outside the buffer reads as OUTSIDE, which differs from every label - and the two voxels next
-// to each quad along x (the row is in the cache by then).  Per voxel: 2 bits of exposed faces per axis.  z and y are the row's,
-// so a thread folds only count, sum x, sum x^2, the three face counts and the surface voxels over its voxels of equal label (its
-// runs, also across the gap between the quads); the lanes of a wave that hold the same label are combined with shuffles and ONE
-// leader lane per (wave, label) turns the seven values into the 14 sums and issues the atomics.
-// Trip counts around the shuffles are wave-uniform (__any / __ballot decide them); there is no workgroup barrier.
+// The sweep layout and the aggregation of cc_fold.h over the rows (z, y) of the measured planes [z_first, z_first + nz) of the
+// buffer.  A wave whose 512 voxels hold no label 1..n stops there.  One that holds a label reads the rows (z-1, y), (z+1, y),
+// (z, y-1) and (z, y+1) at the same x - a row outside the buffer reads as NO_VOXEL, which differs from every label - and the
+// two voxels next to each quad along x (the row is in the cache by then: plain loads, not nontemporal ones).  Per voxel: 2 bits
+// of exposed faces per axis.  A thread folds count, sum x, sum x^2, the three face counts and the surface voxels over its voxels
+// of equal label (its runs, also across the gap between the quads); the leader lane of a (wave, label) turns the seven values
+// into the 14 sums and issues the atomics.  There is no workgroup barrier.
 __global__ void __launch_bounds__(256) cc_shape_kernel(const u32* __restrict__ labels, int Zb, int Y, int X, int z_first, int nz,
                                                        u32 z_abs0, u32 n, u32* __restrict__ counts, u64* __restrict__ sums,
                                                        u64* __restrict__ moments, u64* __restrict__ faces,
                                                        u32* __restrict__ surface) {
-    const int lane = threadIdx.x & 63;
-    const u32 T = blockDim.x;
     const u64 nrows = (u64)nz * Y;
     const u64 plane = (u64)Y * X;
-    const int sweeps = (X + (int)T * IPT - 1) / ((int)T * IPT);
+    const int sweeps = row_sweeps(X);
     for (u64 r = blockIdx.x; r < nrows; r += gridDim.x) {
         const u32 z = (u32)z_first + (u32)(r / (u64)Y), y = (u32)(r % (u64)Y);  // (the buffer's own)
         const u32* lrow = labels + (u64)z * plane + (u64)y * X;
         const bool has_zm = z > 0, has_zp = z + 1 < (u32)Zb, has_ym = y > 0, has_yp = y + 1 < (u32)Y;
         const u64 za = (u64)z_abs0 + z, ya = y;  // (absolute coordinates, <= 65535)
         for (int sw = 0; sw < sweeps; ++sw) {
-            // quad q of this thread starts at xq[q]; voxel k = 4q + j sits at xq[q] + j
-            const u32 xq[2] = {(u32)sw * T * IPT + 4u * threadIdx.x, (u32)sw * T * IPT + 4u * (T + threadIdx.x)};
-            u32 l[IPT];
-            load_quads(lrow, true, xq, (u32)X, l);
-            unsigned todo = 0;  // bit k: voxel k holds a label 1..n that is not folded yet
-#pragma unroll
-            for (int k = 0; k < IPT; ++k) todo |= ((l[k] != 0 && l[k] <= n) ? 1u : 0u) << k;
+            u32 xq[2], l[VPT];
+            quad_starts(sw, xq);
+            load_quads<false>(lrow, true, xq, (u32)X, l);
+            unsigned todo = fg_mask(l, n);    // the voxels that are not folded yet
             if (!__any(todo != 0)) continue;  // (wave-uniform) nothing to measure in this wave's 512 voxels
-            u32 e[IPT];  // exposed faces of voxel k: z in bits 0-1, y in bits 2-3, x in bits 4-5
+            u32 e[VPT];  // exposed faces of voxel k: z in bits 0-1, y in bits 2-3, x in bits 4-5
             {
-                u32 a[IPT], b[IPT];
-                load_quads(has_zm ? lrow - plane : lrow, has_zm, xq, (u32)X, a);
-                load_quads(has_zp ? lrow + plane : lrow, has_zp, xq, (u32)X, b);
+                u32 a[VPT], b[VPT];
+                load_quads<false>(has_zm ? lrow - plane : lrow, has_zm, xq, (u32)X, a);
+                load_quads<false>(has_zp ? lrow + plane : lrow, has_zp, xq, (u32)X, b);
 #pragma unroll
-                for (int k = 0; k < IPT; ++k) e[k] = (a[k] != l[k] ? 1u : 0u) + (b[k] != l[k] ? 1u : 0u);
-                load_quads(has_ym ? lrow - X : lrow, has_ym, xq, (u32)X, a);
-                load_quads(has_yp ? lrow + X : lrow, has_yp, xq, (u32)X, b);
+                for (int k = 0; k < VPT; ++k) e[k] = (a[k] != l[k] ? 1u : 0u) + (b[k] != l[k] ? 1u : 0u);
+                load_quads<false>(has_ym ? lrow - X : lrow, has_ym, xq, (u32)X, a);
+                load_quads<false>(has_yp ? lrow + X : lrow, has_yp, xq, (u32)X, b);
 #pragma unroll
-                for (int k = 0; k < IPT; ++k) e[k] |= ((a[k] != l[k] ? 1u : 0u) + (b[k] != l[k] ? 1u : 0u)) << 2;
+                for (int k = 0; k < VPT; ++k) e[k] |= ((a[k] != l[k] ? 1u : 0u) + (b[k] != l[k] ? 1u : 0u)) << 2;
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     // the voxels before and after the quad (xq - 1 < X also keeps a quad past the row's end inside the row)
-                    const u32 left = (xq[q] > 0 && xq[q] - 1u < (u32)X) ? lrow[xq[q] - 1u] : OUTSIDE;
-                    const u32 right = (xq[q] + 4u < (u32)X) ? lrow[xq[q] + 4u] : OUTSIDE;
+                    const u32 left = (xq[q] > 0 && xq[q] - 1u < (u32)X) ? lrow[xq[q] - 1u] : NO_VOXEL;
+                    const u32 right = (xq[q] + 4u < (u32)X) ? lrow[xq[q] + 4u] : NO_VOXEL;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const u32 lo = j == 0 ? left : l[4 * q + j - 1], hi = j == 3 ? right : l[4 * q + j + 1];
@@ -100,19 +80,15 @@ __global__ void __launch_bounds__(256) cc_shape_kernel(const u32* __restrict__ l
                 }
             }
             // one pass per distinct label of the thread (one, as a rule)
-            while (true) {
+            while (__any(todo != 0)) {
                 const bool have = todo != 0;
-                if (!__any(have)) break;
-                const int k0 = __ffs((int)todo) - 1;
-                u32 lab = 0;
-#pragma unroll
-                for (int k = 0; k < IPT; ++k) lab = (k == k0) ? l[k] : lab;  // (no dynamic index into the registers)
+                const u32 lab = first_label(l, todo);
                 u32 c = 0, sx = 0, fz = 0, fy = 0, fx = 0, sv = 0;  // (<= 8, 8 * 65535, 16, 16, 16, 8)
                 u64 sxx = 0;
 #pragma unroll
-                for (int k = 0; k < IPT; ++k) {
+                for (int k = 0; k < VPT; ++k) {
                     const bool in = ((todo >> k) & 1u) && l[k] == lab;
-                    const u32 x = xq[k >> 2] + (u32)(k & 3);  // (< X <= 65536 where `in`)
+                    const u32 x = voxel_x(xq, k);  // (< X <= 65536 where `in`)
                     c += in ? 1u : 0u;
                     sx += in ? x : 0u;
                     sxx += in ? (u64)(x * x) : 0ull;  // (65535^2 < 2^32)
@@ -122,52 +98,28 @@ __global__ void __launch_bounds__(256) cc_shape_kernel(const u32* __restrict__ l
                     sv += (in && e[k] != 0) ? 1u : 0u;
                     todo &= ~((in ? 1u : 0u) << k);
                 }
-                // lanes holding the same label are combined; one leader per distinct label issues the atomics
-                bool pending = have;
-                while (true) {
-                    const unsigned long long m = __ballot(pending);
-                    if (!m) break;
-                    const int leader = __ffsll((long long)m) - 1;
-                    const u32 L = __shfl(lab, leader, 64);
-                    const bool mine = pending && lab == L;
-                    u32 wc = mine ? (c | (sv << 16)) : 0u;   // (count and surface voxels <= 512 per wave: 16 bits each)
-                    u32 wf = mine ? (fz | (fy << 16)) : 0u;  // (faces per axis <= 1024 per wave)
-                    u32 wfx = mine ? fx : 0u;
-                    u32 wsx = mine ? sx : 0u;  // (<= 512 * 65535: fits 32 bits)
-                    u64 wsxx = mine ? sxx : 0ull;
-                    // (wave-uniform) a label that one lane alone holds - a cell's one run in this stretch of the row, the common
-                    // case of a cell mask - needs no reduction: the leader's own values are the wave's
-                    if (__popcll(__ballot(mine)) > 1)
-                        for (int o = 32; o > 0; o >>= 1) {
-                            wc += __shfl_xor(wc, o, 64);
-                            wf += __shfl_xor(wf, o, 64);
-                            wfx += __shfl_xor(wfx, o, 64);
-                            wsx += __shfl_xor(wsx, o, 64);
-                            wsxx += shfl_xor64(wsxx, o);
-                        }
-                    if (lane == leader) {
-                        const u64 cnt = wc & 0xffffu, s = wsx;
-                        atomicAdd(counts + L, (u32)cnt);
-                        u64* S = sums + 3ull * L;
-                        atomicAdd(S + 0, cnt * za);
-                        atomicAdd(S + 1, cnt * ya);
-                        atomicAdd(S + 2, s);
-                        u64* M = moments + 6ull * L;  // zz, yy, xx, zy, zx, yx
-                        atomicAdd(M + 0, cnt * (za * za));
-                        atomicAdd(M + 1, cnt * (ya * ya));
-                        atomicAdd(M + 2, wsxx);
-                        atomicAdd(M + 3, cnt * (za * ya));
-                        atomicAdd(M + 4, za * s);
-                        atomicAdd(M + 5, ya * s);
-                        // (the inside of a large component exposes nothing)
-                        u64* F = faces + 3ull * L;
-                        if (wf & 0xffffu) atomicAdd(F + 0, (u64)(wf & 0xffffu));
-                        if (wf >> 16) atomicAdd(F + 1, (u64)(wf >> 16));
-                        if (wfx) atomicAdd(F + 2, (u64)wfx);
-                        if (wc >> 16) atomicAdd(surface + L, wc >> 16);
-                    }
-                    pending = pending && !mine;
-                }
+                const ShapeAcc own = {c | (sv << 16), fz | (fy << 16), fx, sx, sxx};
+                wave_fold_by_label<true>(lab, have, own, [&](u32 L, const ShapeAcc& w) {
+                    const u64 cnt = w.c_sv & 0xffffu, s = w.sx;
+                    atomicAdd(counts + L, (u32)cnt);
+                    u64* S = sums + 3ull * L;
+                    atomicAdd(S + 0, cnt * za);
+                    atomicAdd(S + 1, cnt * ya);
+                    atomicAdd(S + 2, s);
+                    u64* M = moments + 6ull * L;  // zz, yy, xx, zy, zx, yx
+                    atomicAdd(M + 0, cnt * (za * za));
+                    atomicAdd(M + 1, cnt * (ya * ya));
+                    atomicAdd(M + 2, w.sxx);
+                    atomicAdd(M + 3, cnt * (za * ya));
+                    atomicAdd(M + 4, za * s);
+                    atomicAdd(M + 5, ya * s);
+                    // (the inside of a large component exposes nothing)
+                    u64* F = faces + 3ull * L;
+                    if (w.fz_fy & 0xffffu) atomicAdd(F + 0, (u64)(w.fz_fy & 0xffffu));
+                    if (w.fz_fy >> 16) atomicAdd(F + 1, (u64)(w.fz_fy >> 16));
+                    if (w.fx) atomicAdd(F + 2, (u64)w.fx);
+                    if (w.c_sv >> 16) atomicAdd(surface + L, w.c_sv >> 16);
+                });
             }
         }
     }

@@ -1,8 +1,8 @@
-// ccl.hip - 26-connected component labelling + per-label statistics on the device.
+// ccl.hip - 26-connected component labelling on the device, the seam merge of slabs labelled on several GPUs and the size
+// filter.  (The per-label statistics of the labels: cc_stats.hip.)
 //
 // Replaces cc3d.connected_components(bin_img, return_N=True) (count_blobs.py:61; cc3d 3.12.3 is a
-// third-party C++ two-pass union-find, not vendored) and cc3d.statistics(..., no_slice_conversion=
-// True) (count_blobs.py:85).  Output contract: label(component) = 1 + rank of its
+// third-party C++ two-pass union-find, not vendored).  Output contract: label(component) = 1 + rank of its
 // minimum linear index z*Y*X + y*X + x among all components; 0 = background.
 //
 // Algorithm: union-find over the voxel index space with atomicMin links (the root of a tree is
@@ -11,8 +11,6 @@
 // work only: results are bit-exact and independent of scheduling.
 #include "common.h"
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
 namespace {
 
@@ -458,141 +456,6 @@ __global__ void __launch_bounds__(256) ccl_bits_of_labels_kernel(const u32* __re
     }
 }
 
-// ---- statistics -------------------------------------------------------------------------------------
-// per label: count, sum z/y/x (u64), bbox min/max (u32).  Contributions are aggregated before they reach memory:
-// each thread folds the runs of equal labels inside its 8 consecutive x voxels, then the lanes of a wave that hold
-// the same label are reduced with shuffles and ONE lane issues the atomics (a mask made of one giant component
-// would otherwise serialise hundreds of millions of atomics on a single address).  Background (label 0) is not
-// accumulated here: its row is derived from the totals on the host, its bounding box by a per-wave reduction.
-constexpr int SPT = 8;  // voxels per thread (one x-run inside a row)
-
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-    const u32 lo = __shfl((u32)v, src, 64), hi = __shfl((u32)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-
-__global__ void __launch_bounds__(256) cc_stats_kernel(const u32* __restrict__ labels, int Z, int Y, int X,
-                                                       u32* __restrict__ counts, u64* __restrict__ sums,
-                                                       u32* __restrict__ bbmin, u32* __restrict__ bbmax) {
-    // a workgroup walks whole rows (z, y): no per-thread 64-bit division, 16-byte loads when the rows allow it; the trip
-    // counts are workgroup-uniform so that the shuffles below are convergent
-    const int segs = (X + SPT - 1) / SPT;
-    const int lane = threadIdx.x & 63;
-    u32 bmin[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, bmax[3] = {0, 0, 0};
-    bool any_bg = false;
-    const bool vec = (X % SPT == 0) && ((reinterpret_cast<uintptr_t>(labels) & 15) == 0);
-    const u64 nrows = (u64)Z * Y;
-    const int sweeps = (segs + (int)blockDim.x - 1) / (int)blockDim.x;
-    for (u64 row = blockIdx.x; row < nrows; row += gridDim.x)
-    for (int sw = 0; sw < sweeps; ++sw) {
-        const int sg = sw * (int)blockDim.x + (int)threadIdx.x;
-        u32 l[SPT];
-        const u32 z = (u32)(row / (u64)Y), y = (u32)(row % (u64)Y);
-        // position of l[k]: x0 + k (+ gap for k >= 4).  Aligned rows: a thread takes voxels [4t, 4t+4) and [4(T+t), 4(T+t)+4) of the
-        // sweep (T threads), so that each of its two 16-byte loads is part of ONE contiguous KiB per wave instruction - with 8
-        // consecutive voxels per thread every instruction touched half of each line (the label volume was read at 3.3 TB/s)
-        const u32 x0 = vec ? (u32)sw * blockDim.x * SPT + 4u * threadIdx.x : (u32)sg * SPT;
-        const u32 gap = vec ? 4u * blockDim.x - 4u : 0u;
-        if (vec) {
-            const u64 base = row * (u64)X + x0;
-            typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
-            u32x4_t u0 = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, u1 = u0;  // pad = "no voxel"
-            if (x0 < (u32)X) u0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(labels + base));
-            if (x0 + 4u + gap < (u32)X) u1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(labels + base + 4 + gap));
-            l[0] = u0.x; l[1] = u0.y; l[2] = u0.z; l[3] = u0.w;
-            l[4] = u1.x; l[5] = u1.y; l[6] = u1.z; l[7] = u1.w;
-        } else if (sg < segs) {
-            const u64 base = row * (u64)X + x0;
-#pragma unroll
-            for (int k = 0; k < SPT; ++k) l[k] = (x0 + k < (u32)X) ? labels[base + k] : 0xffffffffu;
-        } else {
-#pragma unroll
-            for (int k = 0; k < SPT; ++k) l[k] = 0xffffffffu;
-        }
-        auto xpos = [&](int k) -> u32 { return x0 + (u32)k + (k >= 4 ? gap : 0u); };
-        // background bookkeeping: the thread's zero voxels as a bit mask, first / last of them along x
-        unsigned zm = 0, fgm = 0;
-#pragma unroll
-        for (int k = 0; k < SPT; ++k) {
-            zm |= (l[k] == 0 ? 1u : 0u) << k;
-            fgm |= ((l[k] != 0 && l[k] != 0xffffffffu) ? 1u : 0u) << k;
-        }
-        if (zm) {
-            any_bg = true;
-            bmin[0] = min(bmin[0], z); bmax[0] = max(bmax[0], z);
-            bmin[1] = min(bmin[1], y); bmax[1] = max(bmax[1], y);
-            bmin[2] = min(bmin[2], xpos(__ffs((int)zm) - 1)); bmax[2] = max(bmax[2], xpos(31 - __clz((int)zm)));
-        }
-        if (!__any(fgm != 0)) continue;  // (wave-uniform) nothing but background in this wave's 512 voxels
-        // runs of equal foreground labels inside the thread's voxels, one run per pass of the loop below
-        int k = 0;
-        while (true) {
-            // next run of this lane (if any)
-            while (k < SPT && (l[k] == 0 || l[k] == 0xffffffffu)) ++k;
-            const bool have = k < SPT;
-            if (!__any(have)) break;
-            u32 lab = 0, cnt = 0, sx = 0, mnx = 0xffffffffu, mxx = 0;
-            if (have) {
-                lab = l[k];
-                while (k < SPT && l[k] == lab) {
-                    ++cnt;
-                    sx += xpos(k);
-                    mnx = min(mnx, xpos(k));
-                    mxx = max(mxx, xpos(k));
-                    ++k;
-                }
-            }
-            // lanes holding the same label are combined; one leader per distinct label issues the atomics
-            bool pending = have;
-            while (true) {
-                const unsigned long long m = __ballot(pending);
-                if (!m) break;
-                const int leader = __ffsll((long long)m) - 1;
-                const u32 L = __shfl(lab, leader, 64);
-                const bool mine = pending && lab == L;
-                u32 c = mine ? cnt : 0;
-                u64 vz = mine ? (u64)z * cnt : 0, vy = mine ? (u64)y * cnt : 0, vx = mine ? (u64)sx : 0;
-                u32 z0 = mine ? z : 0xffffffffu, z1 = mine ? z : 0, y0 = mine ? y : 0xffffffffu, y1 = mine ? y : 0;
-                u32 xa = mine ? mnx : 0xffffffffu, xb = mine ? mxx : 0;
-                for (int o = 32; o > 0; o >>= 1) {
-                    c += __shfl_xor(c, o, 64);
-                    vz += shfl64(vz, lane ^ o);
-                    vy += shfl64(vy, lane ^ o);
-                    vx += shfl64(vx, lane ^ o);
-                    z0 = min(z0, __shfl_xor(z0, o, 64)); z1 = max(z1, __shfl_xor(z1, o, 64));
-                    y0 = min(y0, __shfl_xor(y0, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
-                    xa = min(xa, __shfl_xor(xa, o, 64)); xb = max(xb, __shfl_xor(xb, o, 64));
-                }
-                if (lane == leader) {
-                    atomicAdd(counts + L, c);
-                    atomicAdd(sums + 3 * (u64)L, vz);
-                    atomicAdd(sums + 3 * (u64)L + 1, vy);
-                    atomicAdd(sums + 3 * (u64)L + 2, vx);
-                    atomicMin(bbmin + 3 * (u64)L, z0); atomicMax(bbmax + 3 * (u64)L, z1);
-                    atomicMin(bbmin + 3 * (u64)L + 1, y0); atomicMax(bbmax + 3 * (u64)L + 1, y1);
-                    atomicMin(bbmin + 3 * (u64)L + 2, xa); atomicMax(bbmax + 3 * (u64)L + 2, xb);
-                }
-                pending = pending && !mine;
-            }
-        }
-    }
-    if (__any(any_bg)) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            u32 lo = bmin[k], hi = bmax[k];
-            for (int o = 32; o > 0; o >>= 1) {
-                lo = min(lo, __shfl_xor(lo, o, 64));
-                hi = max(hi, __shfl_xor(hi, o, 64));
-            }
-            if (lane == 0) {
-                atomicMin(bbmin + k, lo);
-                atomicMax(bbmax + k, hi);
-            }
-        }
-    }
-}
-
-
 // ---- multi-GPU seam merge: slabs are labelled independently; these kernels supply the pairs of
 // labels that touch across a slab boundary and apply the global renumbering --------------------------------------
 // a = labels of the last plane of the upper slab, b = labels of the first plane of the slab below it.  Every
@@ -652,89 +515,8 @@ __global__ void __launch_bounds__(256) relabel_lut_kernel(u32* __restrict__ labe
     }
 }
 
-// ---- size filter (count_blobs' min_size / max_size; cc3d.dust): voxel count per label, keep flags, order-preserving
-// renumbering of the kept labels through a lookup table ----------------------------------------------------------
-// cc_stats_kernel's aggregation with ONE atomic per (wave, label) instead of ten: a thread folds the runs of equal labels in
-// its 8 voxels, the lanes of a wave that hold the same label add up with shuffles and one lane issues the atomicAdd.  The
-// volume is walked as a flat array in tiles of 2048 voxels (a thread takes voxels [4t, 4t+4) and [1024 + 4t, 1024 + 4t + 4)
-// of the tile: every 16-byte load instruction of a wave covers one contiguous KiB); the last partial tile, and every tile of a
-// volume that does not start on a 16-byte boundary, is read label by label.  Labels above n are not counted (the table has
-// n + 1 rows); 0xffffffff stands for "no voxel".
-constexpr int CPT = 8;             // voxels per thread
-constexpr int CTILE = 256 * CPT;   // voxels per workgroup and sweep
-
-__device__ __forceinline__ void cc_counts_fold(const u32 (&l)[CPT], u32 n, u32* __restrict__ counts, u32& nbg) {
-    const int lane = threadIdx.x & 63;
-    // bit k of chg: voxel k starts a run (differs from the voxel before it); bit k of fgm: voxel k holds a label 1..n
-    unsigned fgm = 0, chg = 1u | (1u << CPT);
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        nbg += l[k] == 0 ? 1u : 0u;
-        fgm |= ((l[k] != 0 && l[k] <= n) ? 1u : 0u) << k;
-        if (k > 0) chg |= (l[k] != l[k - 1] ? 1u : 0u) << k;
-    }
-    unsigned starts = fgm & chg;  // first voxels of this thread's foreground runs
-    if (!__any(starts != 0)) return;  // (wave-uniform) nothing but background in this wave's 512 voxels
-    while (true) {
-        const bool have = starts != 0;
-        if (!__any(have)) break;
-        u32 lab = 0, cnt = 0;
-        if (have) {
-            const int k0 = __ffs((int)starts) - 1;
-            starts &= starts - 1;
-            cnt = (u32)(__ffs((int)(chg >> (k0 + 1))) - 1) + 1u;  // up to the next run's start (bit CPT ends the last one)
-            lab = l[0];
-#pragma unroll
-            for (int k = 1; k < CPT; ++k) lab = (k0 == k) ? l[k] : lab;  // (no dynamic index into the registers)
-        }
-        // lanes holding the same label are combined; one leader per distinct label issues the atomic
-        bool pending = have;
-        while (true) {
-            const unsigned long long m = __ballot(pending);
-            if (!m) break;
-            const int leader = __ffsll((long long)m) - 1;
-            const u32 L = __shfl(lab, leader, 64);
-            const bool mine = pending && lab == L;
-            u32 c = mine ? cnt : 0;
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-            if (lane == leader) atomicAdd(counts + L, c);
-            pending = pending && !mine;
-        }
-    }
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(256) cc_counts_kernel(const u32* __restrict__ labels, u64 nvox, u32 n, u32* __restrict__ counts) {
-    const u64 ntiles = nvox / CTILE;
-    u32 nbg = 0;
-    u32 l[CPT];
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (workgroup-uniform trip count: the shuffles are convergent)
-        const u64 base = tile * CTILE + 4u * threadIdx.x;
-        if (VEC) {
-            typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
-            const u32x4_t u0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(labels + base));
-            const u32x4_t u1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(labels + base + CTILE / 2));
-            l[0] = u0.x; l[1] = u0.y; l[2] = u0.z; l[3] = u0.w;
-            l[4] = u1.x; l[5] = u1.y; l[6] = u1.z; l[7] = u1.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                l[k] = labels[base + k];
-                l[4 + k] = labels[base + CTILE / 2 + k];
-            }
-        }
-        cc_counts_fold(l, n, counts, nbg);
-    }
-    if (blockIdx.x == gridDim.x - 1 && ntiles * CTILE < nvox) {  // the last partial tile
-        const u64 base = ntiles * CTILE + (u64)threadIdx.x * CPT;
-#pragma unroll
-        for (int k = 0; k < CPT; ++k) l[k] = base + k < nvox ? labels[base + k] : 0xffffffffu;
-        cc_counts_fold(l, n, counts, nbg);
-    }
-    for (int o = 32; o > 0; o >>= 1) nbg += __shfl_xor(nbg, o, 64);
-    if ((threadIdx.x & 63) == 0 && nbg) atomicAdd(counts, nbg);
-}
-
+// ---- size filter (count_blobs' min_size / max_size; cc3d.dust): keep flags from the voxel count per label (dlv_cc_counts_dev,
+// cc_stats.hip), order-preserving renumbering of the kept labels through a lookup table ---------------------------------------
 // The lookup table of the size filter is made in three launches over the same n + 1 rows, in this order: size_keep_kernel writes
 // the keep flags, the ccl_scan_* kernels turn them into their exclusive prefix sum (the number of kept labels below each label),
 // size_lut_kernel turns that into the new label.  Both kernels ask size_keeps(), so that they cannot disagree about a label.
@@ -752,16 +534,6 @@ __global__ void __launch_bounds__(256) size_lut_kernel(const u32* __restrict__ c
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (u64)gridDim.x * blockDim.x)
         lut[i] = size_keeps(counts, i, lo, hi) ? lut[i] + 1u : 0u;
 }
-
-// shared by dlv_cc_stats_dev / dlv_cc_stats_raw_dev: raw per-label accumulators copied to the host
-struct StatsRaw {
-    std::vector<char> host;
-    size_t off_min, off_max, off_sum, rows;
-    const u32* counts() const { return (const u32*)host.data(); }
-    const u32* bbmin() const { return (const u32*)(host.data() + off_min); }
-    const u32* bbmax() const { return (const u32*)(host.data() + off_max); }
-    const u64* sums() const { return (const u64*)(host.data() + off_sum); }
-};
 
 // The scratch of a labelling of n voxels (slot WS_CCL): root counts per renumbering block, their group sums, the two bit masks
 // (foreground, roots), the chunk list - 0.5 B per voxel.  The union-find's parent array IS the label volume
@@ -883,83 +655,6 @@ int dlv_ccl26_dev(dlv_ctx* ctx, const uint8_t* mask_dev, int Z, int Y, int X, ui
     return DLV_OK;
 }
 
-static int cc_stats_raw(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, StatsRaw& r) {
-    if (Z <= 0 || Y <= 0 || X <= 0) return dlv_fail(ctx, DLV_EINVAL, "empty volume");
-    DLV_HIP(ctx, hipSetDevice(ctx->device));
-    const u64 nvox = (u64)Z * Y * X;
-    const size_t rows = (size_t)n + 1;
-    // [counts u32 rows | bbmin u32 3*rows | bbmax u32 3*rows | pad | sums u64 3*rows]
-    r.rows = rows;
-    r.off_min = rows * 4;
-    r.off_max = r.off_min + rows * 12;
-    r.off_sum = (r.off_max + rows * 12 + 7) & ~(size_t)7;
-    const size_t bytes = r.off_sum + rows * 24;
-    char* ws;
-    DLV_TRY(dlv_ws_get(ctx, WS_MISC, bytes, (void**)&ws));
-    DLV_HIP(ctx, hipMemsetAsync(ws, 0, bytes, ctx->stream));
-    DLV_HIP(ctx, hipMemsetAsync(ws + r.off_min, 0xff, rows * 12, ctx->stream));
-    u32* counts = (u32*)ws;
-    u32* bbmin = (u32*)(ws + r.off_min);
-    u32* bbmax = (u32*)(ws + r.off_max);
-    u64* sums = (u64*)(ws + r.off_sum);
-    const u64 nitems = (u64)Z * Y * ((X + SPT - 1) / SPT);
-    const int gs = (int)std::min<u64>((nitems + 255) / 256, (u64)256 * 32);
-    DlvProf pr(ctx, "cc_stats", 0.0, (double)nvox * 4);
-    hipLaunchKernelGGL(cc_stats_kernel, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, Z, Y, X, counts, sums, bbmin, bbmax);
-    pr.end();
-    DLV_LAUNCH_CHECK(ctx, "cc_stats_kernel");
-    r.host.resize(bytes);
-    DLV_HIP(ctx, hipMemcpyAsync(r.host.data(), ws, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DLV_OK;
-}
-
-int dlv_cc_stats_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, uint32_t* voxel_counts,
-                     uint16_t* bounding_boxes, double* centroids) {
-    if (!ctx || !labels_dev || !voxel_counts || !bounding_boxes || !centroids) return DLV_EINVAL;
-    if (Z > 65536 || Y > 65536 || X > 65536) return dlv_fail(ctx, DLV_EUNSUP, "bounding boxes are uint16");
-    StatsRaw r;
-    DLV_TRY(cc_stats_raw(ctx, labels_dev, Z, Y, X, n, r));
-    const u64 nvox = (u64)Z * Y * X;
-    const size_t rows = r.rows;
-    const u32 *hc = r.counts(), *hmin = r.bbmin(), *hmax = r.bbmax();
-    const u64* hs = r.sums();
-    u64 fg = 0, fs[3] = {0, 0, 0};
-    for (size_t l = 1; l < rows; ++l) {
-        voxel_counts[l] = hc[l];
-        fg += hc[l];
-        for (int k = 0; k < 3; ++k) {
-            fs[k] += hs[3 * l + k];
-            bounding_boxes[6 * l + 2 * k] = (uint16_t)hmin[3 * l + k];
-            bounding_boxes[6 * l + 2 * k + 1] = (uint16_t)hmax[3 * l + k];
-            centroids[3 * l + k] = hc[l] ? (double)hs[3 * l + k] / (double)hc[l] : NAN;
-        }
-    }
-    // background row: totals minus the foreground
-    const u64 dims[3] = {(u64)Z, (u64)Y, (u64)X};
-    const u64 bgc = nvox - fg;
-    voxel_counts[0] = (uint32_t)bgc;
-    for (int k = 0; k < 3; ++k) {
-        const u64 all = (nvox / dims[k]) * (dims[k] * (dims[k] - 1) / 2);
-        centroids[k] = bgc ? (double)(all - fs[k]) / (double)bgc : NAN;
-        bounding_boxes[2 * k] = bgc ? (uint16_t)hmin[k] : 0;
-        bounding_boxes[2 * k + 1] = bgc ? (uint16_t)hmax[k] : 0;
-    }
-    return DLV_OK;
-}
-
-int dlv_cc_stats_raw_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, uint32_t* counts,
-                         uint32_t* bbmin, uint32_t* bbmax, uint64_t* sums) {
-    if (!ctx || !labels_dev || !counts || !bbmin || !bbmax || !sums) return DLV_EINVAL;
-    StatsRaw r;
-    DLV_TRY(cc_stats_raw(ctx, labels_dev, Z, Y, X, n, r));
-    memcpy(counts, r.counts(), r.rows * 4);
-    memcpy(bbmin, r.bbmin(), r.rows * 12);
-    memcpy(bbmax, r.bbmax(), r.rows * 12);
-    memcpy(sums, r.sums(), r.rows * 24);
-    return DLV_OK;
-}
-
 int dlv_seam_pairs_dev(dlv_ctx* ctx, const uint32_t* plane_a_dev, const uint32_t* plane_b_dev, int Y, int X,
                        uint32_t* pairs_dev, uint64_t cap, uint64_t* count_out) {
     if (!ctx || !plane_a_dev || !plane_b_dev || !count_out) return DLV_EINVAL;
@@ -986,24 +681,6 @@ int dlv_relabel_u32_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, const
     const int gs = (int)std::min<u64>((nvox / 4 + 255) / 256 + 1, (u64)256 * 32);
     hipLaunchKernelGGL(relabel_lut_kernel, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, lut_dev, 0u);
     DLV_LAUNCH_CHECK(ctx, "relabel_lut_kernel");
-    return DLV_OK;
-}
-
-int dlv_cc_counts_dev(dlv_ctx* ctx, const uint32_t* labels_dev, uint64_t nvox, uint64_t n, uint32_t* counts_dev) {
-    if (!ctx || !labels_dev || !counts_dev) return DLV_EINVAL;
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_counts: n = %llu does not fit the uint32 labels", (unsigned long long)n);
-    if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "labels must be 4-byte aligned");
-    DLV_HIP(ctx, hipSetDevice(ctx->device));
-    DLV_HIP(ctx, hipMemsetAsync(counts_dev, 0, ((size_t)n + 1) * 4, ctx->stream));
-    if (nvox == 0) return DLV_OK;
-    const int gs = (int)std::min<u64>(std::max<u64>(nvox / CTILE, 1), (u64)256 * 32);
-    DlvProf pr(ctx, "cc_counts", 0.0, (double)nvox * 4);
-    if (((uintptr_t)labels_dev & 15) == 0)
-        hipLaunchKernelGGL(cc_counts_kernel<true>, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, (u32)n, counts_dev);
-    else
-        hipLaunchKernelGGL(cc_counts_kernel<false>, dim3(gs), dim3(256), 0, ctx->stream, labels_dev, (u64)nvox, (u32)n, counts_dev);
-    pr.end();
-    DLV_LAUNCH_CHECK(ctx, "cc_counts_kernel");
     return DLV_OK;
 }
 

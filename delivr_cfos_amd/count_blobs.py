@@ -14,12 +14,15 @@ import pickle
 import numpy as np
 
 from . import hostio
-from .hostlogic import (INTENSITY_KEYS, SHAPE_KEYS, SHELL_KEYS, background_shell_radius, cell_intensity_csv_text, cell_shape_csv_text,
-                        cells_csv_bytes, csv_name, finish_intensity, finish_shape, finish_shell, finish_split, intensity_stats_enabled,
-                        merge_intensity, merge_shape, merge_shell, shape_stats_enabled, size_filter_bounds, split_fused_settings)
+from .hostlogic import (INTENSITY_KEYS, QUARTILE_KEYS, QUARTILE_LEVELS, SHAPE_KEYS, SHELL_KEYS, SHELL_QUARTILE_KEYS, background_shell_radius,
+                        cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, csv_name, finish_intensity,
+                        finish_quartiles, finish_shape, finish_shell, finish_shell_quartiles, finish_split, intensity_quartiles_enabled,
+                        intensity_stats_enabled, merge_intensity, merge_shape, merge_shell, shape_stats_enabled, size_filter_bounds,
+                        split_fused_settings)
 
 _INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
 _SHELL_STATS_KEYS = SHELL_KEYS + ("shell_radius",)  # ... and settings["mi355x"]["background_shell"]
+_SHELL_QUARTILE_STATS_KEYS = SHELL_QUARTILE_KEYS + ("shell_radius",)  # ... and both with settings["mi355x"]["intensity_quartiles"]
 
 
 def _shell_bytes_per_voxel(radius: int) -> int:
@@ -114,24 +117,52 @@ def _open_raw_volume(settings, brain, shape):
     return vol, path
 
 
-def _shell_of(eng, labels_dev, raw_dev, N, radius, keep=None):
+def _quartiles_of(eng, labels_dev, raw_dev, N, timer):
+    """HipEngine.cc_quantiles' pair for hostlogic.QUARTILE_LEVELS; timer: a one-entry list, the seconds spent in here are added"""
+    import time
+
+    t0 = time.perf_counter()
+    pair = eng.cc_quantiles(labels_dev, raw_dev, N, QUARTILE_LEVELS)
+    timer[0] += time.perf_counter() - t0
+    return pair
+
+
+def _shell_of(eng, labels_dev, raw_dev, N, radius, keep=None, moments=True, quartiles=None):
     """the shells of radius `radius` around the cells of labels_dev, measured: (HipEngine.cc_intensity's dict of the shell volume,
     its voxel counts per label 0..N as uint32) - hostlogic.finish_shell's / merge_shell's input.  keep: (first, planes) - the
-    planes of labels_dev whose shell counts (a slab extended by its neighbours' planes: the shell of the slab alone)"""
+    planes of labels_dev whose shell counts (a slab extended by its neighbours' planes: the shell of the slab alone).
+    moments False: None instead of the pair.  quartiles: a timer (_quartiles_of) - the shell volume's quartiles are taken while it
+    lives and (pair or None, _quartiles_of's pair) is returned"""
     shell = eng.cc_shell(labels_dev, radius, raw_dev)
     if keep is not None:
         shell, raw_dev = shell[keep[0]:keep[0] + keep[1]], raw_dev[keep[0]:keep[0] + keep[1]]
-    return eng.cc_intensity(shell, raw_dev, N), eng.cc_counts(shell, N).cpu().numpy().view(np.uint32)
+    pair = (eng.cc_intensity(shell, raw_dev, N), eng.cc_counts(shell, N).cpu().numpy().view(np.uint32)) if moments else None
+    return pair if quartiles is None else (pair, _quartiles_of(eng, shell, raw_dev, N, quartiles))
 
 
 def _intensity_of(eng, labels_dev, raw_planes, N, cells=True, shell_radius=0):
     """raw_planes: the planes of the raw memmap that lie under labels_dev (whole planes: the Y / X padding stays, the pitches
     describe it), uploaded once -> (HipEngine.cc_intensity's dict of the cells, or None without `cells`; _shell_of's pair, or
     None with shell_radius 0); the raw tensor is gone when this returns"""
+    return _intensity_and_quartiles_of(eng, labels_dev, raw_planes, N, cells, shell_radius, shell_radius > 0, False, False)[:2]
+
+
+def _intensity_and_quartiles_of(eng, labels_dev, raw_planes, N, cells, shell_radius, shell, cell_quartiles, shell_quartiles):
+    """_intensity_of, also with settings["mi355x"]["intensity_quartiles"]: one upload of the raw planes serves the moment statistics of the
+    cells (`cells`) and of the shells (`shell`) and the quartiles of either (`cell_quartiles`, `shell_quartiles`; the shell volume is
+    built once for whatever is asked of it) -> (cells' dict | None, _shell_of's pair | None, _quartiles_of's pair of the cells | None,
+    ... of the shells | None, seconds spent in HipEngine.cc_quantiles)"""
     raw_dev = hostio.upload(eng, raw_planes, what="h2d_raw")
+    timer = [0.0]
     try:
         part = eng.cc_intensity(labels_dev, raw_dev, N) if cells else None
-        return part, (_shell_of(eng, labels_dev, raw_dev, N, shell_radius) if shell_radius else None)
+        cell_q = _quartiles_of(eng, labels_dev, raw_dev, N, timer) if cell_quartiles else None
+        shell_part = shell_q = None
+        if shell_quartiles:
+            shell_part, shell_q = _shell_of(eng, labels_dev, raw_dev, N, shell_radius, moments=shell, quartiles=timer)
+        elif shell:
+            shell_part = _shell_of(eng, labels_dev, raw_dev, N, shell_radius)
+        return part, shell_part, cell_q, shell_q, timer[0]
     finally:
         del raw_dev
 
@@ -186,6 +217,16 @@ def _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius=0):
     count_blobs.last_intensity = {"n": int(N), "raw_file": raw_file}
     if shell_radius:
         count_blobs.last_intensity["shell_radius"] = int(shell_radius)
+
+
+def _write_quartiles_table(path_out, brain, stats, N, shell_radius=0):
+    """<output_location>/cell_quartiles/<brain>.csv - in a sub-folder, for _write_intensity_table's reason"""
+    folder = os.path.join(path_out, "cell_quartiles")
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
+        # (shell entries of a cached pickle do not reach the table of a run without the key)
+        fh.write(cell_quartiles_csv_text(stats if shell_radius else {k: v for k, v in stats.items() if k not in SHELL_QUARTILE_KEYS}, N))
+    count_blobs.last_quartiles = {"n": int(N)}
 
 
 def _write_shape_table(path_out, brain, stats, N):
@@ -374,6 +415,15 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     them.  Needs no further volume in HBM; a mask that needs the slab-streamed path is refused; under torch.distributed every slab
     must hold a plane.  Off or absent: nothing of this happens.
 
+    ``settings["mi355x"]["intensity_quartiles"]`` true (with intensity_stats on): order statistics beside the moments.  With a cell's m
+    raw values sorted ascending, level p reads v[(p * (m - 1)) // 100] - the lower quantile, a value the cell holds - taken on the
+    device on the final labels (HipEngine.cc_quantiles).  The pickle gains intensity_q25 / intensity_median / intensity_q75 (uint16,
+    N+1 rows, row 0 zero) and, with background_shell, shell_q25 / shell_median / shell_q75 (0 without a shell) and contrast_median
+    (= intensity_median / shell_median, 0.0 without a shell); the table goes to <output_location>/cell_quartiles/<brain>.csv and
+    ``count_blobs.last_quartiles`` holds {"n"}.  Cached labels are measured too, and a cached pickle without the keys - or, with a
+    shell, with another shell_radius - is completed.  Budgeted as 2 more bytes of HBM per voxel; refused with ValueError on every
+    rank under torch.distributed: quantiles of the parts of a cell cut by a slab do not combine.  Off or absent: nothing of this happens.
+
     ``settings["mi355x"]["split_fused"]`` = d (1..16; ``split_min_core`` = m, default 1): fused cells are split on the device right
     after the labelling, before the size filter, so that min_size / max_size apply to the final cells.  The labels are eroded d
     times with the 6 face neighbours (outside the volume counts as background); what is left are the cores, 26-connected, those of
@@ -391,7 +441,9 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
 
     bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
     shell_radius = background_shell_radius(settings)  # (raises on a bad value, or without intensity_stats, before any file is touched)
+    quartiles_on = intensity_quartiles_enabled(settings)  # (raises on a non-bool, or without intensity_stats, before any file is touched)
     count_blobs.last_filter = None  # set by a run that filtered
+    count_blobs.last_quartiles = None  # set by a run with settings["mi355x"]["intensity_quartiles"]
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
     count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
@@ -414,6 +466,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['split_fused'] = {split[0]} is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
                          "its own; run step 3 on one device or switch split_fused off")
+    if sharded and quartiles_on:
+        # (as for split_fused: all raise, before any collective, or none does)
+        raise ValueError(f"count_blobs: settings['mi355x']['intensity_quartiles'] is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): the values of a cell that crosses a slab cut lie on two ranks, and quantiles "
+                         "of parts do not combine; run step 3 on one device or switch intensity_quartiles off")
     if sharded and shell_radius:
         # every rank computes the same slabs: all raise, before any collective, or none does
         thin = [hi - lo for lo, hi in _even_slabs(shape[0], dist.get_world_size()) if hi - lo < shell_radius]
@@ -496,12 +553,14 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         import time
 
         N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol, shell_radius,
-                                                       shape_on, split)
+                                                       shape_on, split, quartiles_on)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
         if raw_vol is not None:
             _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
+        if quartiles_on:
+            _write_quartiles_table(path_out, brain, stats, N, shell_radius)
         if shape_on:
             _write_shape_table(path_out, brain, stats, N)
         count_blobs.last_timings["csv_s"] = time.perf_counter() - t_csv
@@ -524,7 +583,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
 
 
 def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0, shape=False,
-                        split=None):
+                        split=None, quartiles=False):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
     made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
@@ -533,7 +592,9 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
     shell_radius: settings["mi355x"]["background_shell"] - the shells around the cells are measured with the same raw tensor.
     shape: settings["mi355x"]["shape_stats"] - the shape accumulators are taken on the labels, fresh or cached, after that.
     split: settings["mi355x"]["split_fused"] (hostlogic.split_fused_settings) - a fresh labelling is split between dlv_ccl26_dev
-    and the size filter; its two scratch volumes are gone before the raw volume is uploaded, so the two peaks do not add."""
+    and the size filter; its two scratch volumes are gone before the raw volume is uploaded, so the two peaks do not add.
+    quartiles: settings["mi355x"]["intensity_quartiles"] - the quartiles of the cells, and of the shells with shell_radius, are taken
+    from the same raw tensor (HipEngine.cc_quantiles: 2 more bytes per foreground voxel in HBM, budgeted as 2 per voxel)."""
     import time
 
     labels_dev = None
@@ -564,6 +625,11 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                               f"per voxel in HBM beside the mask, its labels and the raw volume "
                               f"({int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv) / 2**30:.1f} GiB), the HBM budget is "
                               f"{budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
+        if quartiles and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv + 2) > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_quartiles'] needs up to 2 more bytes per voxel in HBM "
+                              f"beside what intensity_stats{' and background_shell' if shell_bpv else ''} need "
+                              f"({int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv + 2) / 2**30:.1f} GiB), the HBM budget is "
+                              f"{budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch intensity_quartiles off")
         if shape and not cached and need > budget:
             raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the mask and its labels in HBM "
                               f"({need / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling "
@@ -671,7 +737,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             with open(path, "wb") as fh:
                 pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
 
-        have_intensity = have_shell = have_shape = False
+        have_intensity = have_shell = have_shape = have_quartiles = have_shell_quartiles = False
         if cached_stats:
             print(f"Found stats at {cached_stats}")
             with open(cached_stats, "rb") as fh:
@@ -680,9 +746,13 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             # (complete only with every shell key and the radius asked for)
             have_shell = all(k in stats for k in _SHELL_STATS_KEYS) and stats["shell_radius"] == shell_radius
             have_shape = all(k in stats for k in SHAPE_KEYS)
+            have_quartiles = all(k in stats for k in QUARTILE_KEYS)
+            have_shell_quartiles = all(k in stats for k in _SHELL_QUARTILE_STATS_KEYS) and stats["shell_radius"] == shell_radius
         measure_cells = raw_vol is not None and not have_intensity
         measure_shell = raw_vol is not None and shell_radius > 0 and not have_shell
-        measure = measure_cells or measure_shell
+        measure_quartiles = quartiles and not have_quartiles
+        measure_shell_quartiles = quartiles and shell_radius > 0 and not have_shell_quartiles
+        measure = measure_cells or measure_shell or measure_quartiles or measure_shell_quartiles
         measure_shape = shape and not have_shape
         if measure_shape and labels_dev is None and int(labels.size) * 4 > budget:
             raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the cached labels in HBM "
@@ -696,6 +766,11 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['background_shell'] = {shell_radius} needs {shell_bpv} more bytes "
                               f"per voxel in HBM beside the cached labels and the raw volume ({int(labels.size) * (6 + shell_bpv) / 2**30:.1f} GiB), "
                               f"the HBM budget is {budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
+        if (measure_quartiles or measure_shell_quartiles) and labels_dev is None and int(labels.size) * (4 + 2 + shell_bpv + 2) > budget:
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_quartiles'] needs up to 2 more bytes per voxel in HBM "
+                              f"beside the cached labels, the raw volume{' and the shell' if shell_bpv else ''} "
+                              f"({int(labels.size) * (8 + shell_bpv) / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
+                              "settings['mi355x']['hbm_budget_gb'] or switch intensity_quartiles off")
         if not cached_stats:
             if labels_dev is None and int(labels.size) * 4 > budget:
                 # cached labels that do not fit the HBM budget: statistics slab by slab (raw sums add up; streaming.py)
@@ -715,16 +790,24 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
         if measure:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
-            part, shell_part = _intensity_of(eng, labels_dev, raw_vol[:Z], N, cells=measure_cells, shell_radius=shell_radius if measure_shell else 0)
+            part, shell_part, cell_q, shell_q, quartiles_s = _intensity_and_quartiles_of(
+                eng, labels_dev, raw_vol[:Z], N, measure_cells, shell_radius, measure_shell, measure_quartiles, measure_shell_quartiles)
             if measure_cells:
                 stats.update(finish_intensity(part, stats["voxel_counts"]))
             if measure_shell:
                 stats.update(finish_shell(*shell_part, stats["intensity_mean"]))
                 stats["shell_radius"] = int(shell_radius)
+            if measure_quartiles:
+                stats.update(finish_quartiles(*cell_q, stats["voxel_counts"]))
+            if measure_shell_quartiles:
+                stats.update(finish_shell_quartiles(*shell_q, stats["shell_voxels"], stats["intensity_median"]))
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
             if not measure_shape:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")
+            if quartiles:  # (HipEngine.cc_quantiles is synchronous: its share of the time since the last mark)
+                tm["intensity_s"] -= quartiles_s
+                tm["quartiles_s"] = quartiles_s
         if measure_shape:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()

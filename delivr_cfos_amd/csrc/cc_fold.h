@@ -1,5 +1,6 @@
-// cc_fold.h - the device pieces the per-label statistics kernels share (cc_stats.hip, cc_intensity.hip, cc_shape.hip): the
-// sweep geometry of a row, its quad loads, and the aggregation of a wave's contributions by label.  Header only, no state.
+// cc_fold.h - the device pieces the per-label statistics kernels share (cc_stats.hip, cc_intensity.hip, cc_shape.hip,
+// cc_quantiles.hip): the sweep geometry of a row, its quad loads, and the aggregation of a wave's contributions by label - folded
+// into one value per label (wave_fold_by_label) or ranked into places (wave_rank_by_label).  Header only, no state.
 //
 // Sweep layout.  A workgroup of T threads walks whole rows (z, y) of the label volume - no per-thread 64-bit division, and
 // arrays of different pitches are addressed from their own row starts.  A row is cut into sweeps of 8 T voxels; in a sweep
@@ -120,6 +121,47 @@ __device__ __forceinline__ void wave_fold_by_label(u32 lab, bool have, const Acc
         if (lane == leader) emit(L, w);
         pending = pending && !mine;
     }
+}
+
+__device__ __forceinline__ u64 shfl64(u64 v, int src) {
+    const u32 lo = __shfl((u32)v, src, 64), hi = __shfl((u32)(v >> 32), src, 64);
+    return ((u64)hi << 32) | lo;
+}
+
+// THE RANK LOOP, the leader loop's twin for a kernel that hands out places instead of folding values (cc_quantiles.hip): a
+// lane that holds cnt items of the label lab learns where they go in the wave's contribution to that label.  leader: the first
+// lane with the label - the one that reserves `total` places with ONE returning atomic; before: the items of the lanes below this
+// one that hold the same label (its exclusive rank); total: the items of all of them.  A lane without `have` names itself as its
+// leader, with total 0.  No atomic is issued in here, so the leaders of all labels of the wave can issue theirs in one instruction
+// afterwards and every lane reads its base with one shuffle from its leader.
+// CONVERGENCE: as for wave_fold_by_label.  A label that one lane alone holds skips the scan.
+struct LabelRank {
+    int leader;
+    u32 before, total;
+};
+__device__ __forceinline__ LabelRank wave_rank_by_label(u32 lab, bool have, u32 cnt) {
+    const int lane = threadIdx.x & 63;
+    LabelRank r = {lane, 0u, 0u};
+    bool pending = have;
+    while (true) {
+        const unsigned long long m = __ballot(pending);
+        if (!m) break;
+        const int leader = __ffsll((long long)m) - 1;
+        const u32 L = __shfl(lab, leader, 64);
+        const bool mine = pending && lab == L;
+        const u32 own = mine ? cnt : 0u;
+        u32 incl = own;
+        const bool single = __popcll(__ballot(mine)) == 1;  // (wave-uniform)
+        if (!single)
+            for (int o = 1; o < 64; o <<= 1) {
+                const u32 up = __shfl_up(incl, o, 64);
+                incl += lane >= o ? up : 0u;
+            }
+        const u32 total = __shfl(incl, single ? leader : 63, 64);
+        if (mine) r = {leader, incl - own, total};
+        pending = pending && !mine;
+    }
+    return r;
 }
 
 }  // namespace

@@ -661,31 +661,56 @@ class HipEngine:
         self._leave()
         return int(kept.value)
 
+    def _labels_under_raw(self, what: str, labels, raw, n):
+        """the tensor checks cc_intensity and cc_quantiles share -> (Z, Y, X, pitch_y, pitch_z, n)"""
+        torch = self.torch
+        for name, t, dtypes in (("labels", labels, (torch.int32,)), ("raw", raw, (torch.uint16, torch.int16))):
+            if not isinstance(t, torch.Tensor) or t.device != self.device:
+                raise ValueError(f"{what}: {name}: expected a torch tensor on {self.device}, got {type(t).__name__} on "
+                                 f"{getattr(t, 'device', None)}")
+            if t.dtype not in dtypes or t.dim() != 3:
+                raise ValueError(f"{what}: {name}: expected a 3-D tensor of {' / '.join(str(d) for d in dtypes)}, got "
+                                 f"{t.dim()}-D {t.dtype}")
+        if not labels.is_contiguous() or labels.numel() == 0:
+            raise ValueError(f"{what}: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
+        Z, Y, X = (int(v) for v in labels.shape)
+        if any(r < v for r, v in zip(raw.shape, (Z, Y, X))):
+            raise ValueError(f"{what}: raw of shape {tuple(raw.shape)} is smaller than the labels {(Z, Y, X)}")
+        pitch_z, pitch_y, pitch_x = (int(s) for s in raw.stride())
+        if pitch_x != 1 or pitch_y < X or pitch_z < Y * pitch_y:
+            raise ValueError(f"{what}: raw with strides {tuple(raw.stride())} is not a (padded) volume with a contiguous last axis")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"{what}: n = {n}")
+        return Z, Y, X, pitch_y, pitch_z, n
+
+    def cc_quantiles(self, labels, raw, n: int, levels=(25, 50, 75)):
+        """Per-label order statistics of the raw volume under a label volume (dlv_cc_quantiles_dev).  labels, raw: as for
+        cc_intensity.  levels: 1..8 integers 0..100 in per cent, strictly increasing; with a label's m raw values sorted ascending,
+        level p reads v[(p * (m - 1)) // 100] - the lower quantile, a value the label holds (50: the lower median, 0 / 100: minimum /
+        maximum).  -> (uint16 array (n+1, len(levels)), uint32 array (n+1,) of the voxels measured per label); row 0 and a label
+        without a voxel read 0 with a count of 0."""
+        Z, Y, X, pitch_y, pitch_z, n = self._labels_under_raw("cc_quantiles", labels, raw, n)
+        levels = list(levels)
+        if (not 1 <= len(levels) <= 8 or any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= int(p) <= 100 for p in levels)
+                or any(int(b) <= int(a) for a, b in zip(levels, levels[1:]))):
+            raise ValueError(f"cc_quantiles: levels = {levels!r}: expected 1..8 integers 0..100, strictly increasing")
+        values = np.zeros((n + 1, len(levels)), dtype=np.uint16)
+        counts = np.zeros(n + 1, dtype=np.uint32)
+        self._enter()
+        self._check(self.lib.dlv_cc_quantiles_dev(self.ctx, C.c_void_p(labels.data_ptr()), C.c_void_p(raw.data_ptr()), Z, Y, X,
+                                                  pitch_y, pitch_z, n, len(levels), (C.c_int * len(levels))(*(int(p) for p in levels)),
+                                                  values.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        self._leave()
+        return values, counts
+
     def cc_intensity(self, labels, raw, n: int) -> dict:
         """Per-label statistics of the raw volume under a label volume (dlv_cc_intensity_dev).  labels: int32 (uint32 payload)
         (Z,Y,X) in HBM; raw: uint16 (or int16-viewed) (Zr,Yr,Xr) in HBM with Zr >= Z, Yr >= Y, Xr >= X, contiguous in its last
         axis - voxel (z,y,x) of the labels is raw[z,y,x], the pitches come from raw's strides (the padded network input, or a view
         into it).  -> {"intensity_sum", "intensity_sumsq": uint64, "intensity_min", "intensity_max": uint16}, n+1 rows each; a label
         without a voxel - and row 0 - reads 0, 0, 0xFFFF, 0."""
-        torch = self.torch
-        for name, t, dtypes in (("labels", labels, (torch.int32,)), ("raw", raw, (torch.uint16, torch.int16))):
-            if not isinstance(t, torch.Tensor) or t.device != self.device:
-                raise ValueError(f"cc_intensity: {name}: expected a torch tensor on {self.device}, got {type(t).__name__} on "
-                                 f"{getattr(t, 'device', None)}")
-            if t.dtype not in dtypes or t.dim() != 3:
-                raise ValueError(f"cc_intensity: {name}: expected a 3-D tensor of {' / '.join(str(d) for d in dtypes)}, got "
-                                 f"{t.dim()}-D {t.dtype}")
-        if not labels.is_contiguous() or labels.numel() == 0:
-            raise ValueError(f"cc_intensity: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
-        Z, Y, X = (int(v) for v in labels.shape)
-        if any(r < v for r, v in zip(raw.shape, (Z, Y, X))):
-            raise ValueError(f"cc_intensity: raw of shape {tuple(raw.shape)} is smaller than the labels {(Z, Y, X)}")
-        pitch_z, pitch_y, pitch_x = (int(s) for s in raw.stride())
-        if pitch_x != 1 or pitch_y < X or pitch_z < Y * pitch_y:
-            raise ValueError(f"cc_intensity: raw with strides {tuple(raw.stride())} is not a (padded) volume with a contiguous last axis")
-        n = int(n)
-        if n < 0:
-            raise ValueError(f"cc_intensity: n = {n}")
+        Z, Y, X, pitch_y, pitch_z, n = self._labels_under_raw("cc_intensity", labels, raw, n)
         out = {"intensity_sum": np.zeros(n + 1, dtype=np.uint64), "intensity_sumsq": np.zeros(n + 1, dtype=np.uint64),
                "intensity_min": np.zeros(n + 1, dtype=np.uint16), "intensity_max": np.zeros(n + 1, dtype=np.uint16)}
         self._enter()

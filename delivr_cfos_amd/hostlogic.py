@@ -205,6 +205,90 @@ def finish_shell(parts: dict, shell_counts, intensity_mean) -> dict:
             "shell_mean": mean, "contrast": contrast}
 
 
+QUARTILE_LEVELS = (25, 50, 75)  # the levels count_blobs asks HipEngine.cc_quantiles for
+QUARTILE_KEYS = ("intensity_q25", "intensity_median", "intensity_q75")  # finish_quartiles' keys
+SHELL_QUARTILE_KEYS = ("shell_q25", "shell_median", "shell_q75", "contrast_median")  # finish_shell_quartiles' keys
+
+
+def intensity_quartiles_enabled(settings) -> bool:
+    """count_blobs' per-cell intensity quartiles: False when settings["mi355x"]["intensity_quartiles"] is absent or false, True
+    when it is true.  ValueError for anything but a bool, and for true without settings["mi355x"]["intensity_stats"]: the
+    quartiles are taken beside the moment statistics, from the raw tensor uploaded for them."""
+    value = ((settings or {}).get("mi355x") or {}).get("intensity_quartiles")
+    if value is None or value is False:
+        return False
+    if value is not True:
+        raise ValueError(f"settings['mi355x']['intensity_quartiles'] = {value!r}: expected true or false")
+    if not intensity_stats_enabled(settings):
+        raise ValueError("settings['mi355x']['intensity_quartiles'] needs settings['mi355x']['intensity_stats']: the quartiles are "
+                         "measured beside the cells' moment statistics")
+    return True
+
+
+def _quartile_columns(values, counts, expected, what: str):
+    """HipEngine.cc_quantiles' pair for QUARTILE_LEVELS, checked against the voxel counts another kernel took -> three uint16
+    columns of N+1 rows, row 0 zero (a label without a voxel reads 0 already)"""
+    values = np.asarray(values)
+    counts, expected = np.asarray(counts).astype(np.uint64), np.asarray(expected).astype(np.uint64)
+    rows = len(expected)
+    if rows < 1 or values.shape != (rows, len(QUARTILE_LEVELS)) or len(counts) != rows:
+        raise RuntimeError(f"{what} quartiles of shape {values.shape} with {len(counts)} counts beside voxel counts of {rows}")
+    bad = np.flatnonzero(counts[1:] != expected[1:]) + 1
+    if len(bad):
+        l = int(bad[0])
+        raise RuntimeError(f"{what} quartiles and voxel counts disagree on {len(bad)} label(s), first label {l}: "
+                           f"{int(expected[l])} voxels counted, {int(counts[l])} measured - labels and statistics of different brains?")
+    cols = [np.array(values[:, k], dtype=np.uint16) for k in range(len(QUARTILE_LEVELS))]
+    for c in cols:
+        c[0] = 0
+    return cols
+
+
+def finish_quartiles(values, counts, voxel_counts) -> dict:
+    """HipEngine.cc_quantiles' (values, counts) of the final labels for the levels QUARTILE_LEVELS -> what count_blobs stores:
+    intensity_q25, intensity_median (the lower median), intensity_q75, uint16, N+1 rows, row 0 zero.  RuntimeError naming the first
+    label when the measured counts and voxel_counts[1:] disagree."""
+    return dict(zip(QUARTILE_KEYS, _quartile_columns(values, counts, voxel_counts, "intensity")))
+
+
+def finish_shell_quartiles(values, counts, shell_voxels, intensity_median) -> dict:
+    """HipEngine.cc_quantiles' pair of the shell volume with finish_shell's shell_voxels and the cells' intensity_median -> shell_q25,
+    shell_median, shell_q75 uint16 (0 for a cell without a shell) and contrast_median float64 = intensity_median / shell_median
+    (0.0 without a shell; a shell voxel is not 0 in the raw volume, so the median of a shell with a voxel is positive).
+    RuntimeError when the measured counts and shell_voxels[1:] disagree."""
+    out = dict(zip(SHELL_QUARTILE_KEYS, _quartile_columns(values, counts, shell_voxels, "shell")))
+    cells = np.asarray(intensity_median)
+    if len(cells) != len(out["shell_median"]):
+        raise RuntimeError(f"shell quartiles of {len(out['shell_median'])} rows beside cell medians of {len(cells)}")
+    present = np.asarray(shell_voxels) != 0
+    present[0] = False
+    contrast = np.zeros(len(cells), dtype=np.float64)
+    np.divide(cells.astype(np.float64), out["shell_median"].astype(np.float64), out=contrast, where=present)
+    out["contrast_median"] = contrast
+    return out
+
+
+def cell_quartiles_csv_text(stats: dict, n: int) -> str:
+    """count_blobs' cell_quartiles/<brain>.csv: header ``Blob,Size,Q25,Median,Q75``, one row per label 1..N - all N, as
+    cell_intensity_csv_text - integers written plainly, every line ended by a newline.  With finish_shell_quartiles' keys and
+    shell_voxels in `stats` the columns ``ShellSize,ShellQ25,ShellMedian,ShellQ75,ContrastMedian`` follow, the float as repr."""
+    n = int(n)
+    cols = [np.asarray(stats[k])[1:n + 1].tolist() for k in ("voxel_counts",) + QUARTILE_KEYS]
+    shell = all(k in stats for k in SHELL_QUARTILE_KEYS + ("shell_voxels",))
+    if shell:
+        cols += [np.asarray(stats[k])[1:n + 1].tolist() for k in ("shell_voxels",) + SHELL_QUARTILE_KEYS[:3]]
+        cols.append(np.asarray(stats["contrast_median"], dtype=np.float64)[1:n + 1].tolist())
+    if any(len(c) != n for c in cols):
+        raise ValueError("statistics shorter than the label count")
+    if not shell:
+        lines = ["Blob,Size,Q25,Median,Q75"]
+        lines.extend(f"{i},{c},{a},{b},{d}" for i, (c, a, b, d) in enumerate(zip(*cols), 1))
+    else:
+        lines = ["Blob,Size,Q25,Median,Q75,ShellSize,ShellQ25,ShellMedian,ShellQ75,ContrastMedian"]
+        lines.extend(f"{i},{c},{a},{b},{d},{sc},{sa},{sb},{sd},{ct!r}" for i, (c, a, b, d, sc, sa, sb, sd, ct) in enumerate(zip(*cols), 1))
+    return "\n".join(lines) + "\n"
+
+
 SPLIT_KEYS = ("split_parent", "split_siblings")  # finish_split's keys
 SPLIT_MAX_DEPTH = 16  # dlv_cc_split_dev's largest depth
 

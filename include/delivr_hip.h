@@ -308,6 +308,18 @@ int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, ui
 int dlv_cc_intensity_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
                          int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n,
                          uint64_t* sum, uint64_t* sumsq, uint16_t* vmin, uint16_t* vmax);
+/* Per-label order statistics of a raw uint16 volume under a label volume (no counterpart in the reference). For a label l with
+ * m >= 1 voxels whose raw values sorted ascending are v[0] <= ... <= v[m-1], and a level p in per cent: Q_p(l) = v[(p * (m - 1)) / 100]
+ * (integer division) - the "lower" quantile, always a value the label holds; p = 50 is the lower median, p = 0 / 100 the minimum /
+ * maximum. labels_dev, raw_dev, the pitches and the alignment rules as for dlv_cc_intensity_dev. levels: host, n_levels = 1..8
+ * integers 0..100, strictly increasing. Host outputs: out uint16 (n+1) x n_levels row-major, counts uint32 n+1 = the voxels
+ * measured per label; row 0 (background) and a label without a voxel read 0 with a count of 0 - the count tells an absent label from
+ * a true 0. Labels above n are not measured. Exact, and independent of scheduling. Device scratch: 2 bytes per foreground voxel, 12
+ * bytes per label and the result table; DLV_ENOMEM names the sizes. A NULL pointer, Z/Y/X < 1, bad pitches, n >= 2^32 - 1, a
+ * misaligned pointer or a bad level list: DLV_EINVAL, nothing written. Synchronous. */
+int dlv_cc_quantiles_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
+                         int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n, int n_levels, const int* levels,
+                         uint16_t* out, uint32_t* counts);
 /* The background shell of every component (no counterpart in the reference): E_0 = labels; E_{k+1}(v) = E_k(v) where that is not
  * 0, else the smallest non-zero E_k over the 26 neighbours of v inside the volume (0 without one), every step from E_k alone;
  * shell(v) = E_radius(v) where labels(v) == 0 and raw(v) != 0, else 0 - the smallest label among the cells nearest to v in

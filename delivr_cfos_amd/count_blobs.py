@@ -10,24 +10,15 @@ from __future__ import annotations
 import datetime
 import os
 import pickle
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 from . import hostio
-from .hostlogic import (INTENSITY_KEYS, QUARTILE_KEYS, QUARTILE_LEVELS, SHAPE_KEYS, SHELL_KEYS, SHELL_QUARTILE_KEYS, background_shell_radius,
-                        cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, csv_name, finish_intensity,
-                        finish_quartiles, finish_shape, finish_shell, finish_shell_quartiles, finish_split, intensity_quartiles_enabled,
-                        intensity_stats_enabled, merge_intensity, merge_shape, merge_shell, shape_stats_enabled, size_filter_bounds,
-                        split_fused_settings)
-
-_INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
-_SHELL_STATS_KEYS = SHELL_KEYS + ("shell_radius",)  # ... and settings["mi355x"]["background_shell"]
-_SHELL_QUARTILE_STATS_KEYS = SHELL_QUARTILE_KEYS + ("shell_radius",)  # ... and both with settings["mi355x"]["intensity_quartiles"]
-
-
-def _shell_bytes_per_voxel(radius: int) -> int:
-    """HBM of HipEngine.cc_shell beside the labels and the raw volume: the shell volume, and the scratch volume above radius 1"""
-    return 0 if not radius else (4 if radius == 1 else 8)
+from .hostlogic import (QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_intensity_csv_text,
+                        cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget, count_options, csv_name,
+                        finish_intensity, finish_quartiles, finish_shape, finish_shell, finish_shell_quartiles, finish_split,
+                        measuring_plan, merge_intensity, merge_shape, merge_shell)
 
 
 def _find_cached(path: str, suffix: str, brain: str):
@@ -65,11 +56,6 @@ def _labels_in_file_dtype(labels_dev, n: int):
 def _even_slabs(Z: int, world: int):
     cuts = [(Z * r) // world for r in range(world + 1)]
     return [(cuts[r], cuts[r + 1]) for r in range(world)]
-
-
-def _filter_active(bounds) -> bool:
-    """bounds: hostlogic.size_filter_bounds' answer - the filter removes something only with the switch on and a bound given"""
-    return bounds is not None and (bounds[0] >= 0 or bounds[1] >= 0)
 
 
 def _keep_mask(counts: np.ndarray, bounds) -> np.ndarray:
@@ -117,54 +103,48 @@ def _open_raw_volume(settings, brain, shape):
     return vol, path
 
 
-def _quartiles_of(eng, labels_dev, raw_dev, N, timer):
-    """HipEngine.cc_quantiles' pair for hostlogic.QUARTILE_LEVELS; timer: a one-entry list, the seconds spent in here are added"""
+class _Measured(NamedTuple):
+    """what _measure_raw took from the raw volume; None for what the plan did not ask for"""
+    cells: Optional[dict]  # HipEngine.cc_intensity's dict of the cells - hostlogic.finish_intensity's / merge_intensity's input
+    shell: Optional[tuple]  # (cc_intensity's dict of the shell volume, its voxel counts per label 0..N as uint32) - finish_shell's / merge_shell's
+    cell_quartiles: Optional[tuple]  # HipEngine.cc_quantiles' pair for hostlogic.QUARTILE_LEVELS, of the cells
+    shell_quartiles: Optional[tuple]  # ... of the shell volume
+    quartiles_s: float  # the seconds spent in cc_quantiles
+
+
+def _measure_raw(eng, labels_dev, raw_planes, N, opts, plan, keep=None) -> _Measured:
+    """raw_planes: the planes of the raw memmap that lie under labels_dev (whole planes: the Y / X padding stays, the pitches
+    describe it).  One upload of them serves whatever `plan` (hostlogic.measuring_plan) asks of the cells and of their shells of
+    radius opts.shell_radius; the shell volume is built once for its moments and its quartiles.  keep: (first, planes) - the planes of
+    labels_dev that count (a slab extended by its neighbours' planes: the cells and the shell of the slab alone).  The raw tensor
+    is gone when this returns."""
     import time
 
-    t0 = time.perf_counter()
-    pair = eng.cc_quantiles(labels_dev, raw_dev, N, QUARTILE_LEVELS)
-    timer[0] += time.perf_counter() - t0
-    return pair
-
-
-def _shell_of(eng, labels_dev, raw_dev, N, radius, keep=None, moments=True, quartiles=None):
-    """the shells of radius `radius` around the cells of labels_dev, measured: (HipEngine.cc_intensity's dict of the shell volume,
-    its voxel counts per label 0..N as uint32) - hostlogic.finish_shell's / merge_shell's input.  keep: (first, planes) - the
-    planes of labels_dev whose shell counts (a slab extended by its neighbours' planes: the shell of the slab alone).
-    moments False: None instead of the pair.  quartiles: a timer (_quartiles_of) - the shell volume's quartiles are taken while it
-    lives and (pair or None, _quartiles_of's pair) is returned"""
-    shell = eng.cc_shell(labels_dev, radius, raw_dev)
-    if keep is not None:
-        shell, raw_dev = shell[keep[0]:keep[0] + keep[1]], raw_dev[keep[0]:keep[0] + keep[1]]
-    pair = (eng.cc_intensity(shell, raw_dev, N), eng.cc_counts(shell, N).cpu().numpy().view(np.uint32)) if moments else None
-    return pair if quartiles is None else (pair, _quartiles_of(eng, shell, raw_dev, N, quartiles))
-
-
-def _intensity_of(eng, labels_dev, raw_planes, N, cells=True, shell_radius=0):
-    """raw_planes: the planes of the raw memmap that lie under labels_dev (whole planes: the Y / X padding stays, the pitches
-    describe it), uploaded once -> (HipEngine.cc_intensity's dict of the cells, or None without `cells`; _shell_of's pair, or
-    None with shell_radius 0); the raw tensor is gone when this returns"""
-    return _intensity_and_quartiles_of(eng, labels_dev, raw_planes, N, cells, shell_radius, shell_radius > 0, False, False)[:2]
-
-
-def _intensity_and_quartiles_of(eng, labels_dev, raw_planes, N, cells, shell_radius, shell, cell_quartiles, shell_quartiles):
-    """_intensity_of, also with settings["mi355x"]["intensity_quartiles"]: one upload of the raw planes serves the moment statistics of the
-    cells (`cells`) and of the shells (`shell`) and the quartiles of either (`cell_quartiles`, `shell_quartiles`; the shell volume is
-    built once for whatever is asked of it) -> (cells' dict | None, _shell_of's pair | None, _quartiles_of's pair of the cells | None,
-    ... of the shells | None, seconds spent in HipEngine.cc_quantiles)"""
     raw_dev = hostio.upload(eng, raw_planes, what="h2d_raw")
-    timer = [0.0]
+    kept = slice(None) if keep is None else slice(keep[0], keep[0] + keep[1])
+    raw_kept = raw_dev[kept]
+    quartiles_s = 0.0
+
+    def quartiles_of(volume):
+        nonlocal quartiles_s
+        t0 = time.perf_counter()
+        pair = eng.cc_quantiles(volume, raw_kept, N, QUARTILE_LEVELS)
+        quartiles_s += time.perf_counter() - t0
+        return pair
+
     try:
-        part = eng.cc_intensity(labels_dev, raw_dev, N) if cells else None
-        cell_q = _quartiles_of(eng, labels_dev, raw_dev, N, timer) if cell_quartiles else None
-        shell_part = shell_q = None
-        if shell_quartiles:
-            shell_part, shell_q = _shell_of(eng, labels_dev, raw_dev, N, shell_radius, moments=shell, quartiles=timer)
-        elif shell:
-            shell_part = _shell_of(eng, labels_dev, raw_dev, N, shell_radius)
-        return part, shell_part, cell_q, shell_q, timer[0]
+        cells = eng.cc_intensity(labels_dev[kept], raw_kept, N) if "cells" in plan else None
+        cell_q = quartiles_of(labels_dev[kept]) if "cell_quartiles" in plan else None
+        shell = shell_q = None
+        if plan & {"shell", "shell_quartiles"}:
+            shell_vol = eng.cc_shell(labels_dev, opts.shell_radius, raw_dev)[kept]
+            if "shell" in plan:
+                shell = (eng.cc_intensity(shell_vol, raw_kept, N), eng.cc_counts(shell_vol, N).cpu().numpy().view(np.uint32))
+            if "shell_quartiles" in plan:
+                shell_q = quartiles_of(shell_vol)
+        return _Measured(cells, shell, cell_q, shell_q, quartiles_s)
     finally:
-        del raw_dev
+        del raw_dev, raw_kept
 
 
 def _slab_with_neighbour_planes(labels, dist, rank, world, radius):
@@ -190,67 +170,55 @@ def _slab_with_neighbour_planes(labels, dist, rank, world, radius):
     return extended, (radius if rank > 0 else 0)
 
 
-def _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, radius):
-    """_intensity_of for the slab [lo, hi) of a sharded run.  The shell of a voxel depends on the labels within `radius` planes
-    of it only, so every rank takes `radius` planes of the final global labels from either neighbour
+def _measure_raw_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, opts, plan) -> _Measured:
+    """_measure_raw for the slab [lo, hi) of a sharded run.  The shell of a voxel depends on the labels within opts.shell_radius
+    planes of it only, so every rank takes that many planes of the final global labels from either neighbour
     (_slab_with_neighbour_planes), expands the extended slab and keeps its own planes - exactly the planes [lo, hi) of the whole
     volume's shell."""
-    if not radius:
-        return _intensity_of(eng, labels, raw_vol[lo:hi], N)
-    extended, first = _slab_with_neighbour_planes(labels, dist, rank, world, radius)
-    raw_dev = hostio.upload(eng, raw_vol[lo - first:lo - first + int(extended.shape[0])], what="h2d_raw")
-    try:
-        part = eng.cc_intensity(labels, raw_dev[first:first + (hi - lo)], N)
-        return part, _shell_of(eng, extended, raw_dev, N, radius, keep=(first, hi - lo))
-    finally:
-        del raw_dev
+    if not opts.shell_radius:
+        return _measure_raw(eng, labels, raw_vol[lo:hi], N, opts, plan)
+    extended, first = _slab_with_neighbour_planes(labels, dist, rank, world, opts.shell_radius)
+    return _measure_raw(eng, extended, raw_vol[lo - first:lo - first + int(extended.shape[0])], N, opts, plan, keep=(first, hi - lo))
 
 
-def _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius=0):
-    """<output_location>/cell_intensity/<brain>.csv - in a sub-folder, so that no cache look-up (_find_cached: any entry with
-    '.npy' / '.pickle' and the brain's name) and no reader of the reference's CSV ever matches it"""
-    folder = os.path.join(path_out, "cell_intensity")
+def _write_table(path_out, folder, brain, text):
+    """<output_location>/<folder>/<brain>.csv - in a sub-folder, so that no cache look-up (_find_cached: any entry with '.npy' /
+    '.pickle' and the brain's name) and no reader of the reference's CSV ever matches it"""
+    folder = os.path.join(path_out, folder)
     os.makedirs(folder, exist_ok=True)
     with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
-        # (shell entries of a cached pickle do not reach the table of a run without the key)
-        fh.write(cell_intensity_csv_text(stats if shell_radius else {k: v for k, v in stats.items() if k not in SHELL_KEYS}, N))
-    count_blobs.last_intensity = {"n": int(N), "raw_file": raw_file}
-    if shell_radius:
-        count_blobs.last_intensity["shell_radius"] = int(shell_radius)
+        fh.write(text)
 
 
-def _write_quartiles_table(path_out, brain, stats, N, shell_radius=0):
-    """<output_location>/cell_quartiles/<brain>.csv - in a sub-folder, for _write_intensity_table's reason"""
-    folder = os.path.join(path_out, "cell_quartiles")
-    os.makedirs(folder, exist_ok=True)
-    with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
-        # (shell entries of a cached pickle do not reach the table of a run without the key)
-        fh.write(cell_quartiles_csv_text(stats if shell_radius else {k: v for k, v in stats.items() if k not in SHELL_QUARTILE_KEYS}, N))
-    count_blobs.last_quartiles = {"n": int(N)}
+def _write_tables(path_out, brain, stats, N, opts, raw_file):
+    """the tables of the opt-in statistics `opts` asks for, and what count_blobs.last_intensity / last_quartiles / last_shape say"""
+    def for_table(shell_keys):  # (shell entries of a cached pickle do not reach the table of a run without the key)
+        return stats if opts.shell_radius else {k: v for k, v in stats.items() if k not in shell_keys}
+
+    if opts.intensity:
+        _write_table(path_out, "cell_intensity", brain, cell_intensity_csv_text(for_table(SHELL_KEYS), N))
+        count_blobs.last_intensity = {"n": int(N), "raw_file": raw_file}
+        if opts.shell_radius:
+            count_blobs.last_intensity["shell_radius"] = int(opts.shell_radius)
+    if opts.quartiles:
+        _write_table(path_out, "cell_quartiles", brain, cell_quartiles_csv_text(for_table(SHELL_QUARTILE_KEYS), N))
+        count_blobs.last_quartiles = {"n": int(N)}
+    if opts.shape:
+        _write_table(path_out, "cell_shape", brain, cell_shape_csv_text(stats, N))
+        count_blobs.last_shape = {"n": int(N)}
 
 
-def _write_shape_table(path_out, brain, stats, N):
-    """<output_location>/cell_shape/<brain>.csv - in a sub-folder, for _write_intensity_table's reason"""
-    folder = os.path.join(path_out, "cell_shape")
-    os.makedirs(folder, exist_ok=True)
-    with open(os.path.join(folder, f"{brain}.csv"), "w", newline="") as fh:
-        fh.write(cell_shape_csv_text(stats, N))
-    count_blobs.last_shape = {"n": int(N)}
-
-
-def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_vol=None, shell_radius=0, shape=False):
+def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts=CountOptions(), raw_vol=None):
     """One process per GPU: every rank labels a Z-slab of the mask, seams are merged (parallel.ccl_sharded) and every
     rank writes ITS label slab straight into the output .npy (rank 0 creates the file once N - and with it the label
     dtype - is known); only the merged statistics travel to rank 0.  No rank ever holds the whole label volume (17 GB for
-    1024x2048x2048).  bounds: the size filter (hostlogic.size_filter_bounds) - every rank counts the voxels of the global
-    labels in its slab, the counts are summed over the ranks, every rank applies the same filter to its slab and the
-    statistics are taken on the filtered labels.  raw_vol: the raw volume (settings["mi355x"]["intensity_stats"]) - every
-    rank measures planes [lo, hi) of it under its final global labels, rank 0 merges the parts into its stats.  shell_radius:
-    settings["mi355x"]["background_shell"] - the shells around the cells are measured too (_intensity_and_shell_of_slab).
-    shape: settings["mi355x"]["shape_stats"] - every rank takes one plane of the final global labels from either neighbour slab
-    (a face of a voxel is exposed or not by its neighbour across the cut), measures its own planes of the extended slab with their
-    absolute z (HipEngine.cc_shape) and rank 0 adds the parts up (every slab holds a plane: count_blobs checked).
-    Returns (N, stats | None)."""
+    1024x2048x2048).  opts: the opt-in keys (hostlogic.CountOptions; count_blobs refused those a slab cannot serve).  Size
+    filter: every rank counts the voxels of the global labels in its slab, the counts are summed over the ranks, every rank
+    applies the same filter to its slab and the statistics are taken on the filtered labels.  Intensity and shell statistics:
+    every rank measures planes [lo, hi) of raw_vol under its final global labels (_measure_raw_of_slab), rank 0 merges the parts
+    into its stats.  Shape statistics: every rank takes one plane of the final global labels from either neighbour slab (a face
+    of a voxel is exposed or not by its neighbour across the cut), measures its own planes of the extended slab with their
+    absolute z (HipEngine.cc_shape) and rank 0 adds the parts up.  Returns (N, stats | None)."""
     from .parallel import ccl_sharded, merge_stats
 
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -258,7 +226,8 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
     slabs = _even_slabs(Z, world)
     lo, hi = slabs[rank]
     slab = hostio.upload(eng, bin_img[lo:hi], what="h2d_mask") if hi > lo else None
-    if not _filter_active(bounds):
+    bounds = opts.bounds
+    if not opts.filter_active:
         labels, N, stats = ccl_sharded(eng, slab, slabs, rank, dist, (Z, Y, X))
     else:
         labels, n_before, _ = ccl_sharded(eng, slab, slabs, rank, dist, (Z, Y, X), want_stats=False)
@@ -297,47 +266,28 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
         stats = None
         if rank == 0:  # (the labels are global and final already: identity tables)
             stats = merge_stats([np.arange(N + 1, dtype=np.uint32)] * world, raws, [s[0] for s in slabs], (Z, Y, X), N)
-    if raw_vol is not None:
-        # (as for the filter: the outcome of every rank's pass, and then of rank 0's merge, is exchanged before the next collective)
-        part, failed = None, None
-        try:
+    if opts.intensity:
+        plan = measuring_plan(opts, None)
+
+        def measure_slab():  # (a rank without a plane has no part)
             if labels is not None:
-                part = _intensity_and_shell_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, shell_radius)
-        except Exception as exc:
-            failed = f"rank {rank}: {exc!r}"
-        _raise_if_any_failed(dist, failed, "count_blobs: the intensity statistics")
-        parts = [None] * world
-        dist.gather_object(part, parts if rank == 0 else None, dst=0)
-        failed = None
-        if rank == 0:
-            try:
-                stats.update(finish_intensity(merge_intensity([p and p[0] for p in parts]), stats["voxel_counts"]))
-                if shell_radius:
-                    stats.update(finish_shell(*merge_shell([p and p[1] for p in parts]), stats["intensity_mean"]))
-                    stats["shell_radius"] = int(shell_radius)
-            except Exception as exc:
-                failed = f"rank 0: {exc!r}"
-        _raise_if_any_failed(dist, failed, "count_blobs: merging the intensity statistics")
-    if shape:
-        # (as for the intensity statistics: every outcome is exchanged before the next collective)
-        part, failed = None, None
-        try:
+                return _measure_raw_of_slab(eng, labels, dist, rank, world, raw_vol, lo, hi, N, opts, plan)
+
+        def merge_measured(parts):
+            stats.update(finish_intensity(merge_intensity([p and p.cells for p in parts]), stats["voxel_counts"]))
+            if opts.shell_radius:
+                stats.update(finish_shell(*merge_shell([p and p.shell for p in parts]), stats["intensity_mean"]))
+                stats["shell_radius"] = int(opts.shell_radius)
+
+        _on_every_slab(dist, "the intensity statistics", measure_slab, merge_measured)
+    if opts.shape:
+        def shape_of_slab():
             if labels is not None:
                 extended, first = _slab_with_neighbour_planes(labels, dist, rank, world, 1)
-                part = eng.cc_shape(extended, N, keep=(first, hi - lo), z_abs0=lo - first)
-                del extended
-        except Exception as exc:
-            failed = f"rank {rank}: {exc!r}"
-        _raise_if_any_failed(dist, failed, "count_blobs: the shape statistics")
-        parts = [None] * world
-        dist.gather_object(part, parts if rank == 0 else None, dst=0)
-        failed = None
-        if rank == 0:
-            try:
-                stats.update(finish_shape(merge_shape(parts), stats["voxel_counts"]))
-            except Exception as exc:
-                failed = f"rank 0: {exc!r}"
-        _raise_if_any_failed(dist, failed, "count_blobs: merging the shape statistics")
+                return eng.cc_shape(extended, N, keep=(first, hi - lo), z_abs0=lo - first)
+
+        _on_every_slab(dist, "the shape statistics", shape_of_slab,
+                       lambda parts: stats.update(finish_shape(merge_shape(parts), stats["voxel_counts"])))
     out_path = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
     err = [None]
     if rank == 0:
@@ -362,6 +312,28 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds=None, raw_v
         mine = f"rank {rank}: {exc!r}"
     _raise_if_any_failed(dist, mine, f"count_blobs: writing the label slabs into {out_path} (path_out must be shared by all ranks)")
     return N, stats
+
+
+def _on_every_slab(dist, what: str, measure, merge):
+    """One statistic of a sharded run: every rank runs measure() for its part (None on a rank without a plane), the parts are
+    gathered on rank 0 and merge(parts) runs there.  The outcome of every rank's pass, and then of rank 0's merge, is exchanged
+    before the next collective: a rank that fails never leaves the others waiting, all raise together."""
+    rank = dist.get_rank()
+    part, failed = None, None
+    try:
+        part = measure()
+    except Exception as exc:
+        failed = f"rank {rank}: {exc!r}"
+    _raise_if_any_failed(dist, failed, f"count_blobs: {what}")
+    parts = [None] * dist.get_world_size()
+    dist.gather_object(part, parts if rank == 0 else None, dst=0)
+    failed = None
+    if rank == 0:
+        try:
+            merge(parts)
+        except Exception as exc:
+            failed = f"rank 0: {exc!r}"
+    _raise_if_any_failed(dist, failed, f"count_blobs: merging {what}")
 
 
 def _raise_if_any_failed(dist, mine, what: str):
@@ -439,17 +411,14 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     this happens."""
     from .engine import shared_engine
 
-    bounds = size_filter_bounds(settings, min_size, max_size)  # (raises on min_size > max_size before any file is touched)
-    shell_radius = background_shell_radius(settings)  # (raises on a bad value, or without intensity_stats, before any file is touched)
-    quartiles_on = intensity_quartiles_enabled(settings)  # (raises on a non-bool, or without intensity_stats, before any file is touched)
     count_blobs.last_filter = None  # set by a run that filtered
     count_blobs.last_quartiles = None  # set by a run with settings["mi355x"]["intensity_quartiles"]
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
     count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
-    split = split_fused_settings(settings)  # (raises on a bad value before any file is touched)
-    shape_on = shape_stats_enabled(settings)
-    if bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
+    opts = count_options(settings, min_size, max_size)  # (a bad key raises here, before any file is touched)
+    split, shell_radius = opts.split, opts.shell_radius
+    if opts.bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
         print(f"min_size {min_size} / max_size {max_size} are ignored, as in the reference; "
               "settings['mi355x']['size_filter'] = true applies them")
 
@@ -466,7 +435,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['split_fused'] = {split[0]} is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
                          "its own; run step 3 on one device or switch split_fused off")
-    if sharded and quartiles_on:
+    if sharded and opts.quartiles:
         # (as for split_fused: all raise, before any collective, or none does)
         raise ValueError(f"count_blobs: settings['mi355x']['intensity_quartiles'] is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): the values of a cell that crosses a slab cut lie on two ranks, and quantiles "
@@ -477,14 +446,14 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         if thin:
             raise ValueError(f"count_blobs: settings['mi355x']['background_shell'] = {shell_radius} needs Z-slabs of at least {shell_radius} "
                              f"planes on every rank, {shape[0]} planes over {dist.get_world_size()} ranks give slabs of {min(thin)}")
-    if sharded and shape_on:
+    if sharded and opts.shape:
         # (a face across a cut is judged from the neighbour slab's plane: the same check with a radius of 1)
         thin = [hi - lo for lo, hi in _even_slabs(shape[0], dist.get_world_size()) if hi - lo < 1]
         if thin:
             raise ValueError(f"count_blobs: settings['mi355x']['shape_stats'] needs Z-slabs of at least 1 plane on every rank, "
                              f"{shape[0]} planes over {dist.get_world_size()} ranks give slabs of {min(thin)}")
     raw_vol, raw_file = None, None
-    if intensity_stats_enabled(settings):  # (before any file is written; under torch.distributed all ranks raise or none does)
+    if opts.intensity:  # (before any file is written; under torch.distributed all ranks raise or none does)
         failed = None
         try:
             raw_vol, raw_file = _open_raw_volume(settings, brain, shape)
@@ -501,7 +470,6 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     print(f"{start} Now postprocessing inference for {brain} - {brain_i}/{len_b}")
     brain_path = os.path.join(path_in, brain, "binary_segmentations", "binaries.npy")
     bin_img = np.memmap(brain_path, dtype=np.uint8, mode="r", shape=shape, offset=128)
-    own = False  # (the shared engine outlives the call)
     eng = engine or shared_engine(int(os.environ.get("LOCAL_RANK", 0)) if sharded else 0)
     if sharded:
         branch = [None]
@@ -512,15 +480,9 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
                 branch[0] = ("error", repr(exc))
         dist.broadcast_object_list(branch, src=0)
         if branch[0][0] == "error":
-            if own:
-                eng.close()
             raise RuntimeError(f"count_blobs: rank 0 failed while looking for a cached labelling: {branch[0][1]}")
         if not branch[0][1]:
-            try:
-                N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, bounds, raw_vol, shell_radius, shape_on)
-            finally:
-                if own:
-                    eng.close()
+            N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts, raw_vol)
             mine = None
             if rank == 0:
                 try:
@@ -528,10 +490,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
                         pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
                     with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
                         fh.write(cells_csv_bytes(stats, N))
-                    if raw_vol is not None:
-                        _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
-                    if shape_on:
-                        _write_shape_table(path_out, brain, stats, N)
+                    _write_tables(path_out, brain, stats, N, opts, raw_file)
                     end = datetime.datetime.now()
                     print(f"{end} {brain} {brain_i} / {len_b} Done ({dist.get_world_size()} ranks); Took {end - start}")
                 except Exception as exc:
@@ -541,8 +500,6 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         if rank != 0:
             # a cached labelling exists: rank 0 alone re-uses it (and writes the statistics / CSV), the others wait for
             # N - or for the error rank 0 ran into
-            if own:
-                eng.close()
             box = [None]
             dist.broadcast_object_list(box, src=0)
             if isinstance(box[0], tuple):
@@ -552,17 +509,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     try:
         import time
 
-        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds, raw_vol, shell_radius,
-                                                       shape_on, split, quartiles_on)
+        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts, raw_vol)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
-        if raw_vol is not None:
-            _write_intensity_table(path_out, brain, stats, N, raw_file, shell_radius)
-        if quartiles_on:
-            _write_quartiles_table(path_out, brain, stats, N, shell_radius)
-        if shape_on:
-            _write_shape_table(path_out, brain, stats, N)
+        _write_tables(path_out, brain, stats, N, opts, raw_file)
         count_blobs.last_timings["csv_s"] = time.perf_counter() - t_csv
         t_join = time.perf_counter()
         if defer_write:
@@ -582,21 +533,17 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bounds=None, raw_vol=None, shell_radius=0, shape=False,
-                        split=None, quartiles=False):
+def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=CountOptions(), raw_vol=None):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
-    made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  bounds: the size
-    filter (hostlogic.size_filter_bounds), applied to a fresh labelling between dlv_ccl26_dev and the label write.  raw_vol: the
-    raw volume (settings["mi355x"]["intensity_stats"]), measured under the labels - fresh or cached - after cc_stats.
-    shell_radius: settings["mi355x"]["background_shell"] - the shells around the cells are measured with the same raw tensor.
-    shape: settings["mi355x"]["shape_stats"] - the shape accumulators are taken on the labels, fresh or cached, after that.
-    split: settings["mi355x"]["split_fused"] (hostlogic.split_fused_settings) - a fresh labelling is split between dlv_ccl26_dev
-    and the size filter; its two scratch volumes are gone before the raw volume is uploaded, so the two peaks do not add.
-    quartiles: settings["mi355x"]["intensity_quartiles"] - the quartiles of the cells, and of the shells with shell_radius, are taken
-    from the same raw tensor (HipEngine.cc_quantiles: 2 more bytes per foreground voxel in HBM, budgeted as 2 per voxel)."""
+    made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  opts: the opt-in keys
+    (hostlogic.CountOptions).  A fresh labelling is split, then filtered, between dlv_ccl26_dev and the label write - the two
+    scratch volumes of the split are gone before the raw volume is uploaded, so the two peaks do not add.  The labels - fresh or
+    cached - are measured after cc_stats: what hostlogic.measuring_plan finds missing, from one upload of raw_vol (_measure_raw),
+    then the shape accumulators; the pickle is written once, after the last of these."""
     import time
 
+    bounds, split = opts.bounds, opts.split
     labels_dev = None
     wait = lambda: None  # noqa: E731
     tm = count_blobs.last_timings = {}
@@ -613,41 +560,13 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
         budget = hbm_budget_bytes(eng, settings)
         need = int(bin_img.size) * ccl_bytes_per_voxel()
         Z = int(bin_img.shape[0])
-        if raw_vol is not None and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 2) > budget:
-            # (the planes of the raw volume sit in HBM beside the labels: 2 more bytes per voxel - and no slab-streamed measuring)
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_stats'] needs the mask, its labels and the raw "
-                              f"volume in HBM ({int(bin_img.size) * (ccl_bytes_per_voxel() + 2) / 2**30:.1f} GiB), the HBM budget is "
-                              f"{budget / 2**30:.1f} GiB and the slab-streamed labelling does not measure; raise "
-                              "settings['mi355x']['hbm_budget_gb'] or switch intensity_stats off")
-        shell_bpv = _shell_bytes_per_voxel(shell_radius)
-        if shell_bpv and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv) > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['background_shell'] = {shell_radius} needs {shell_bpv} more bytes "
-                              f"per voxel in HBM beside the mask, its labels and the raw volume "
-                              f"({int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv) / 2**30:.1f} GiB), the HBM budget is "
-                              f"{budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
-        if quartiles and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv + 2) > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_quartiles'] needs up to 2 more bytes per voxel in HBM "
-                              f"beside what intensity_stats{' and background_shell' if shell_bpv else ''} need "
-                              f"({int(bin_img.size) * (ccl_bytes_per_voxel() + 2 + shell_bpv + 2) / 2**30:.1f} GiB), the HBM budget is "
-                              f"{budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch intensity_quartiles off")
-        if shape and not cached and need > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the mask and its labels in HBM "
-                              f"({need / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling "
-                              "does not measure; raise settings['mi355x']['hbm_budget_gb'] or switch shape_stats off")
-        if split is not None and not cached and int(bin_img.size) * (ccl_bytes_per_voxel() + 8) > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['split_fused'] = {split[0]} needs 8 more bytes per voxel in HBM "
-                              f"beside the mask and its labels ({int(bin_img.size) * (ccl_bytes_per_voxel() + 8) / 2**30:.1f} GiB), the HBM "
-                              f"budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling does not split; raise "
-                              "settings['mi355x']['hbm_budget_gb'] or switch split_fused off")
+        if not cached:  # (size_filter is judged here too: refused exactly when the mask would be slab-streamed)
+            check_hbm_budget(opts, measuring_plan(opts, None), False, ccl_bytes_per_voxel(), int(bin_img.size), budget)
         if not cached and need > budget:
             # the mask + its uint32 labels do not fit this GPU: Z-slabs through the device, seams merged on the host
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
             plane = int(bin_img.shape[1]) * int(bin_img.shape[2]) * ccl_bytes_per_voxel()
             n_slabs = -(-need // max(budget, 1))
-            if _filter_active(bounds):
-                raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['size_filter'] needs the mask and its labels in HBM "
-                                  f"({need / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB and the slab-streamed labelling "
-                                  "does not filter; raise settings['mi355x']['hbm_budget_gb'] or switch size_filter off")
             if plane > budget or n_slabs > bin_img.shape[0]:
                 raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): one mask plane with its labels and scratch needs {plane / 2**20:.1f} MiB, "
                                   f"the HBM budget is {budget / 2**20:.1f} MiB; raise settings['mi355x']['hbm_budget_gb']")
@@ -683,7 +602,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
                 N, split_parent, components_split = eng.cc_split(labels_dev, N, split[0], split[1])
                 _note_split(split, n_components, N, components_split)
                 mark("split")
-            if _filter_active(bounds):
+            if opts.filter_active:
                 n_before = N
                 counts_dev = eng.cc_counts(labels_dev, N)
                 N = eng.cc_size_filter(labels_dev, N, bounds[0], bounds[1], counts=counts_dev)
@@ -714,7 +633,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
         else:
             N = int(cached.split("/")[-1].split("-")[1])
             print(f"Cached brain found at {cached} with {N} components, loading...")
-            if _filter_active(bounds):
+            if opts.filter_active:
                 print(f"size filter: the cached labelling is reused as it is, min_size {bounds[0]} / max_size {bounds[1]} are not applied to it")
             if split is not None:
                 print(f"split of fused cells: the cached labelling is reused as it is, it is not split (depth {split[0]}) again")
@@ -737,40 +656,14 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             with open(path, "wb") as fh:
                 pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
 
-        have_intensity = have_shell = have_shape = have_quartiles = have_shell_quartiles = False
+        stats = None
         if cached_stats:
             print(f"Found stats at {cached_stats}")
             with open(cached_stats, "rb") as fh:
                 stats = pickle.load(fh)
-            have_intensity = all(k in stats for k in _INTENSITY_STATS_KEYS)
-            # (complete only with every shell key and the radius asked for)
-            have_shell = all(k in stats for k in _SHELL_STATS_KEYS) and stats["shell_radius"] == shell_radius
-            have_shape = all(k in stats for k in SHAPE_KEYS)
-            have_quartiles = all(k in stats for k in QUARTILE_KEYS)
-            have_shell_quartiles = all(k in stats for k in _SHELL_QUARTILE_STATS_KEYS) and stats["shell_radius"] == shell_radius
-        measure_cells = raw_vol is not None and not have_intensity
-        measure_shell = raw_vol is not None and shell_radius > 0 and not have_shell
-        measure_quartiles = quartiles and not have_quartiles
-        measure_shell_quartiles = quartiles and shell_radius > 0 and not have_shell_quartiles
-        measure = measure_cells or measure_shell or measure_quartiles or measure_shell_quartiles
-        measure_shape = shape and not have_shape
-        if measure_shape and labels_dev is None and int(labels.size) * 4 > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['shape_stats'] needs the cached labels in HBM "
-                              f"({int(labels.size) * 4 / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
-                              "settings['mi355x']['hbm_budget_gb'] or switch shape_stats off")
-        if measure and labels_dev is None and int(labels.size) * (4 + 2) > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_stats'] needs the cached labels and the raw volume "
-                              f"in HBM ({int(labels.size) * 6 / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
-                              "settings['mi355x']['hbm_budget_gb'] or switch intensity_stats off")
-        if measure_shell and labels_dev is None and int(labels.size) * (4 + 2 + shell_bpv) > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['background_shell'] = {shell_radius} needs {shell_bpv} more bytes "
-                              f"per voxel in HBM beside the cached labels and the raw volume ({int(labels.size) * (6 + shell_bpv) / 2**30:.1f} GiB), "
-                              f"the HBM budget is {budget / 2**30:.1f} GiB; raise settings['mi355x']['hbm_budget_gb'] or switch background_shell off")
-        if (measure_quartiles or measure_shell_quartiles) and labels_dev is None and int(labels.size) * (4 + 2 + shell_bpv + 2) > budget:
-            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['intensity_quartiles'] needs up to 2 more bytes per voxel in HBM "
-                              f"beside the cached labels, the raw volume{' and the shell' if shell_bpv else ''} "
-                              f"({int(labels.size) * (8 + shell_bpv) / 2**30:.1f} GiB), the HBM budget is {budget / 2**30:.1f} GiB; raise "
-                              "settings['mi355x']['hbm_budget_gb'] or switch intensity_quartiles off")
+        plan = measuring_plan(opts, stats)  # (what the cached pickle lacks; without one, all that is asked for)
+        if labels_dev is None:
+            check_hbm_budget(opts, plan, True, 4, int(labels.size), budget)
         if not cached_stats:
             if labels_dev is None and int(labels.size) * 4 > budget:
                 # cached labels that do not fit the HBM budget: statistics slab by slab (raw sums add up; streaming.py)
@@ -784,31 +677,30 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
             if split_parent is not None:
                 stats.update(finish_split(split_parent, count_blobs.last_split["n_before"]))
                 stats["split_depth"] = int(split[0])
-            if not measure and not measure_shape:
+            if not plan:
                 write_stats(os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("stats")
-        if measure:
+        if plan & RAW_GROUPS:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
-            part, shell_part, cell_q, shell_q, quartiles_s = _intensity_and_quartiles_of(
-                eng, labels_dev, raw_vol[:Z], N, measure_cells, shell_radius, measure_shell, measure_quartiles, measure_shell_quartiles)
-            if measure_cells:
-                stats.update(finish_intensity(part, stats["voxel_counts"]))
-            if measure_shell:
-                stats.update(finish_shell(*shell_part, stats["intensity_mean"]))
-                stats["shell_radius"] = int(shell_radius)
-            if measure_quartiles:
-                stats.update(finish_quartiles(*cell_q, stats["voxel_counts"]))
-            if measure_shell_quartiles:
-                stats.update(finish_shell_quartiles(*shell_q, stats["shell_voxels"], stats["intensity_median"]))
+            got = _measure_raw(eng, labels_dev, raw_vol[:Z], N, opts, plan)
+            if got.cells is not None:
+                stats.update(finish_intensity(got.cells, stats["voxel_counts"]))
+            if got.shell is not None:
+                stats.update(finish_shell(*got.shell, stats["intensity_mean"]))
+                stats["shell_radius"] = int(opts.shell_radius)
+            if got.cell_quartiles is not None:
+                stats.update(finish_quartiles(*got.cell_quartiles, stats["voxel_counts"]))
+            if got.shell_quartiles is not None:
+                stats.update(finish_shell_quartiles(*got.shell_quartiles, stats["shell_voxels"], stats["intensity_median"]))
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
-            if not measure_shape:
+            if "shape" not in plan:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")
-            if quartiles:  # (HipEngine.cc_quantiles is synchronous: its share of the time since the last mark)
-                tm["intensity_s"] -= quartiles_s
-                tm["quartiles_s"] = quartiles_s
-        if measure_shape:
+            if opts.quartiles:  # (HipEngine.cc_quantiles is synchronous: its share of the time since the last mark)
+                tm["intensity_s"] -= got.quartiles_s
+                tm["quartiles_s"] = got.quartiles_s
+        if "shape" in plan:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
             stats.update(finish_shape(eng.cc_shape(labels_dev, N), stats["voxel_counts"]))
@@ -820,9 +712,6 @@ def _count_blobs_single(settings, brain, bin_img, eng, own, path_out, start, bou
         except Exception:
             pass
         raise
-    finally:
-        if own:
-            eng.close()
     # note: the reference takes min_size / max_size and never reads them (count_blobs.py:105); here they apply with
     # settings["mi355x"]["size_filter"] (above, right after the labelling)
     return N, stats, wait

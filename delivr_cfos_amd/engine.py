@@ -661,10 +661,10 @@ class HipEngine:
         self._leave()
         return int(kept.value)
 
-    def _labels_under_raw(self, what: str, labels, raw, n):
-        """the tensor checks cc_intensity and cc_quantiles share -> (Z, Y, X, pitch_y, pitch_z, n)"""
+    def _label_volume(self, what: str, labels, *raw):
+        """the tensor checks of a label volume in HBM, and of the raw volume(s) given beside it -> (Z, Y, X)"""
         torch = self.torch
-        for name, t, dtypes in (("labels", labels, (torch.int32,)), ("raw", raw, (torch.uint16, torch.int16))):
+        for name, t, dtypes in (("labels", labels, (torch.int32,)),) + tuple(("raw", r, (torch.uint16, torch.int16)) for r in raw):
             if not isinstance(t, torch.Tensor) or t.device != self.device:
                 raise ValueError(f"{what}: {name}: expected a torch tensor on {self.device}, got {type(t).__name__} on "
                                  f"{getattr(t, 'device', None)}")
@@ -673,12 +673,23 @@ class HipEngine:
                                  f"{t.dim()}-D {t.dtype}")
         if not labels.is_contiguous() or labels.numel() == 0:
             raise ValueError(f"{what}: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
-        Z, Y, X = (int(v) for v in labels.shape)
+        return tuple(int(v) for v in labels.shape)
+
+    @staticmethod
+    def _raw_pitches(what: str, raw, shape):
+        """the raw volume (a tensor: _label_volume checked) holds a label volume of `shape` -> (pitch_y, pitch_z)"""
+        Z, Y, X = shape
         if any(r < v for r, v in zip(raw.shape, (Z, Y, X))):
             raise ValueError(f"{what}: raw of shape {tuple(raw.shape)} is smaller than the labels {(Z, Y, X)}")
         pitch_z, pitch_y, pitch_x = (int(s) for s in raw.stride())
         if pitch_x != 1 or pitch_y < X or pitch_z < Y * pitch_y:
             raise ValueError(f"{what}: raw with strides {tuple(raw.stride())} is not a (padded) volume with a contiguous last axis")
+        return pitch_y, pitch_z
+
+    def _labels_under_raw(self, what: str, labels, raw, n):
+        """the checks cc_intensity and cc_quantiles share -> (Z, Y, X, pitch_y, pitch_z, n)"""
+        Z, Y, X = self._label_volume(what, labels, raw)
+        pitch_y, pitch_z = self._raw_pitches(what, raw, (Z, Y, X))
         n = int(n)
         if n < 0:
             raise ValueError(f"{what}: n = {n}")
@@ -727,25 +738,8 @@ class HipEngine:
         tensor (uint32 payload) of the labels' shape in HBM; cc_intensity / cc_counts on it measure the shells.  Needs one more
         volume of that size while it runs when radius > 1."""
         torch = self.torch
-        for name, t, dtypes in (("labels", labels, (torch.int32,)), ("raw", raw, (torch.uint16, torch.int16))):
-            if t is None and name == "raw":
-                continue
-            if not isinstance(t, torch.Tensor) or t.device != self.device:
-                raise ValueError(f"cc_shell: {name}: expected a torch tensor on {self.device}, got {type(t).__name__} on "
-                                 f"{getattr(t, 'device', None)}")
-            if t.dtype not in dtypes or t.dim() != 3:
-                raise ValueError(f"cc_shell: {name}: expected a 3-D tensor of {' / '.join(str(d) for d in dtypes)}, got "
-                                 f"{t.dim()}-D {t.dtype}")
-        if not labels.is_contiguous() or labels.numel() == 0:
-            raise ValueError(f"cc_shell: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
-        Z, Y, X = (int(v) for v in labels.shape)
-        pitch_z = pitch_y = 0
-        if raw is not None:
-            if any(r < v for r, v in zip(raw.shape, (Z, Y, X))):
-                raise ValueError(f"cc_shell: raw of shape {tuple(raw.shape)} is smaller than the labels {(Z, Y, X)}")
-            pitch_z, pitch_y, pitch_x = (int(s) for s in raw.stride())
-            if pitch_x != 1 or pitch_y < X or pitch_z < Y * pitch_y:
-                raise ValueError(f"cc_shell: raw with strides {tuple(raw.stride())} is not a (padded) volume with a contiguous last axis")
+        Z, Y, X = self._label_volume("cc_shell", labels, *(() if raw is None else (raw,)))
+        pitch_y, pitch_z = (0, 0) if raw is None else self._raw_pitches("cc_shell", raw, (Z, Y, X))
         if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 16:
             raise ValueError(f"cc_shell: radius = {radius!r}: expected an integer 1..16")
         radius = int(radius)
@@ -765,15 +759,7 @@ class HipEngine:
         -> {"shape_counts": uint32 (n+1), "shape_sums": uint64 (n+1,3) = sum z, y, x, "shape_moments": uint64 (n+1,6) = sum zz,
         yy, xx, zy, zx, yx, "shape_faces": uint64 (n+1,3) = exposed faces per axis z, y, x, "shape_surface_voxels": uint32 (n+1)};
         row 0 and a label without a measured voxel are all zero, so slabs add up (hostlogic.merge_shape)."""
-        torch = self.torch
-        if not isinstance(labels, torch.Tensor) or labels.device != self.device:
-            raise ValueError(f"cc_shape: labels: expected a torch tensor on {self.device}, got {type(labels).__name__} on "
-                             f"{getattr(labels, 'device', None)}")
-        if labels.dtype != torch.int32 or labels.dim() != 3:
-            raise ValueError(f"cc_shape: labels: expected a 3-D tensor of {torch.int32}, got {labels.dim()}-D {labels.dtype}")
-        if not labels.is_contiguous() or labels.numel() == 0:
-            raise ValueError(f"cc_shape: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
-        Z, Y, X = (int(v) for v in labels.shape)
+        Z, Y, X = self._label_volume("cc_shape", labels)
         first, planes = (0, Z) if keep is None else (int(keep[0]), int(keep[1]))
         if first < 0 or planes < 1 or first + planes > Z:
             raise ValueError(f"cc_shape: keep = {keep!r} does not select planes of the {Z} in the buffer")
@@ -798,13 +784,7 @@ class HipEngine:
         -> (K, parent: uint32 ndarray of K+1 with parent[j] = the old label of piece j and parent[0] = 0, the number of labels
         that were split).  Needs two more volumes of the labels' size while it runs."""
         torch = self.torch
-        if not isinstance(labels, torch.Tensor) or labels.device != self.device:
-            raise ValueError(f"cc_split: labels: expected a torch tensor on {self.device}, got {type(labels).__name__} on "
-                             f"{getattr(labels, 'device', None)}")
-        if labels.dtype != torch.int32 or labels.dim() != 3:
-            raise ValueError(f"cc_split: labels: expected a 3-D tensor of {torch.int32}, got {labels.dim()}-D {labels.dtype}")
-        if not labels.is_contiguous() or labels.numel() == 0:
-            raise ValueError(f"cc_split: labels of shape {tuple(labels.shape)} must be contiguous and not empty")
+        Z, Y, X = self._label_volume("cc_split", labels)
         if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= 16:
             raise ValueError(f"cc_split: depth = {depth!r}: expected an integer 1..16")
         if isinstance(min_core, bool) or not isinstance(min_core, (int, np.integer)) or int(min_core) < 1:
@@ -812,7 +792,6 @@ class HipEngine:
         n = int(n)
         if n < 0:
             raise ValueError(f"cc_split: n = {n}")
-        Z, Y, X = (int(v) for v in labels.shape)
         work_a = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
         work_b = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
         k, n_split = C.c_uint64(), C.c_uint64()

@@ -1,6 +1,7 @@
 """Host-side integer logic of the path that the reference performs in Python (no device work)."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -478,6 +479,98 @@ def cell_shape_csv_text(stats: dict, n: int) -> str:
     lines.extend(f"{i},{c},{fz},{fy},{fx},{sv},{a0!r},{a1!r},{a2!r},{el!r},{sp!r}"
                  for i, (c, fz, fy, fx, sv, a0, a1, a2, el, sp) in enumerate(zip(*ints, *floats), 1))
     return "\n".join(lines) + "\n"
+
+
+@dataclass(frozen=True)
+class CountOptions:
+    """count_blobs' opt-in keys of settings["mi355x"], each as its parser returns it (count_options builds the record from the
+    settings); the defaults are a run without any key"""
+    bounds: Optional[Tuple[int, int]] = None  # size_filter_bounds
+    intensity: bool = False  # intensity_stats_enabled
+    shell_radius: int = 0  # background_shell_radius
+    quartiles: bool = False  # intensity_quartiles_enabled
+    shape: bool = False  # shape_stats_enabled
+    split: Optional[Tuple[int, int]] = None  # split_fused_settings
+
+    @property
+    def filter_active(self) -> bool:
+        """the size filter removes something only with the switch on and a bound given"""
+        return self.bounds is not None and (self.bounds[0] >= 0 or self.bounds[1] >= 0)
+
+    @property
+    def shell_bytes_per_voxel(self) -> int:
+        """HBM of HipEngine.cc_shell beside the labels and the raw volume: the shell volume, and the scratch volume above radius 1"""
+        return 0 if not self.shell_radius else (4 if self.shell_radius == 1 else 8)
+
+
+def count_options(settings, min_size, max_size) -> CountOptions:
+    """The record of count_blobs' opt-in keys.  The parsers run in this order, so with several bad keys the first one's ValueError
+    is raised."""
+    bounds = size_filter_bounds(settings, min_size, max_size)
+    shell_radius = background_shell_radius(settings)
+    quartiles = intensity_quartiles_enabled(settings)
+    split = split_fused_settings(settings)
+    shape = shape_stats_enabled(settings)
+    return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
+                        shape=shape, split=split)
+
+
+INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
+SHELL_STATS_KEYS = SHELL_KEYS + ("shell_radius",)  # ... and settings["mi355x"]["background_shell"]
+SHELL_QUARTILE_STATS_KEYS = SHELL_QUARTILE_KEYS + ("shell_radius",)  # ... and both with settings["mi355x"]["intensity_quartiles"]
+RAW_GROUPS = frozenset(("cells", "shell", "cell_quartiles", "shell_quartiles"))  # the groups of measuring_plan taken from the raw volume
+
+
+def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
+    """The groups of per-cell statistics count_blobs has to measure: those `opts` asks for and `stats` - the cached pickle, None
+    without one - does not hold completely.  A group is complete with every key of its row; a row that lists shell_radius also needs
+    the radius asked for (shells of another radius are other shells)."""
+    shell = opts.shell_radius > 0
+    rows = (("cells", opts.intensity, INTENSITY_STATS_KEYS),
+            ("shell", opts.intensity and shell, SHELL_STATS_KEYS),
+            ("cell_quartiles", opts.quartiles, QUARTILE_KEYS),
+            ("shell_quartiles", opts.quartiles and shell, SHELL_QUARTILE_STATS_KEYS),
+            ("shape", opts.shape, SHAPE_KEYS))
+
+    def complete(keys) -> bool:
+        return (stats is not None and all(k in stats for k in keys)
+                and ("shell_radius" not in keys or stats["shell_radius"] == opts.shell_radius))
+
+    return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
+
+
+_HBM_FRESH = ("intensity_stats", "background_shell", "intensity_quartiles", "shape_stats", "split_fused", "size_filter")
+_HBM_CACHED = ("shape_stats", "intensity_stats", "background_shell", "intensity_quartiles")  # (cached labels are not split or filtered)
+
+
+def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxels: int, budget: int) -> None:
+    """count_blobs' HBM check of the opt-in keys.  Resident are `base` bytes per voxel: the mask and its labels of a fresh labelling
+    (streaming.ccl_bytes_per_voxel()), or the cached labels (4).  measured: the groups (measuring_plan) that are going to be taken -
+    of a fresh labelling all that are asked for, measuring_plan(opts, None).  MemoryError for the first key, in the order the work
+    is done, whose volumes do not fit `budget` bytes beside that; a fresh labelling above the budget alone is slab-streamed
+    (streaming.py), which measures, splits and filters nothing."""
+    resident = "the cached labels" if cached else "the mask and its labels"
+    raw = bool(RAW_GROUPS & measured)
+    s = opts.shell_bytes_per_voxel
+    rows = {  # key: (it applies, its value in the settings, bytes per voxel beside the resident ones, what it needs, what streaming lacks)
+        "intensity_stats": (raw, "", 2, f"the raw volume in HBM beside {resident}", "measure"),
+        "background_shell": ("shell" in measured, f" = {opts.shell_radius}", 2 + s,
+                             f"{s} more bytes per voxel in HBM beside {resident} and the raw volume", None),
+        "intensity_quartiles": (bool(measured & {"cell_quartiles", "shell_quartiles"}), "", 2 + s + 2,
+                                f"up to 2 more bytes per voxel in HBM beside {resident}, the raw volume{' and the shell' if s else ''}", None),
+        "shape_stats": ("shape" in measured, "", 0, f"{resident} in HBM", "measure"),
+        "split_fused": (opts.split is not None, f" = {opts.split and opts.split[0]}", 8,
+                        f"8 more bytes per voxel in HBM beside {resident}", "split"),
+        "size_filter": (opts.filter_active, "", 0, f"{resident} in HBM", "filter"),
+    }
+    for key in _HBM_CACHED if cached else _HBM_FRESH:
+        applies, value, extra, clause, lacks = rows[key]
+        need = int(voxels) * (int(base) + extra)
+        if applies and need > budget:
+            streamed = f" and the slab-streamed labelling does not {lacks}" if lacks and not cached else ""
+            raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): settings['mi355x']['{key}']{value} needs {clause} ({need / 2**30:.1f} GiB), "
+                              f"the HBM budget is {budget / 2**30:.1f} GiB{streamed}; raise settings['mi355x']['hbm_budget_gb'] or "
+                              f"switch {key} off")
 
 
 def pass_schedule(tta: bool) -> List[Tuple[Optional[int], int]]:

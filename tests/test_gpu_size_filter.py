@@ -347,11 +347,12 @@ def _run_thread_ranks(fake, body):
 
 def test_sharded_count_blobs_with_bounds_equals_the_single_engine_result(eng, tmp_path):
     from delivr_cfos_amd.count_blobs import _count_blobs_sharded, count_blobs
+    from delivr_cfos_amd.hostlogic import CountOptions
 
     m, lo, hi, world = _seam_volume()
     expected, k_ref, st1, last = _single_engine_reference(eng, m, lo, hi, world)
     fake = _ThreadRanks(world)
-    results = _run_thread_ranks(fake, lambda rank, e: _count_blobs_sharded(e, m, fake, str(tmp_path), "b", bounds=(lo, hi)))
+    results = _run_thread_ranks(fake, lambda rank, e: _count_blobs_sharded(e, m, fake, str(tmp_path), "b", opts=CountOptions(bounds=(lo, hi))))
     assert all(r[0] == k_ref for r in results)
     assert results[1][1] is None and results[2][1] is None
     assert sorted(os.listdir(str(tmp_path))) == [f"b-{k_ref}-cc3d.npy"]

@@ -91,6 +91,12 @@ class DebugLayerArgs(C.Structure):
         ("B", C.c_int), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int),
         ("ran_zreg", C.c_int), ("ran_upconv", C.c_int), ("ran_stem", C.c_int), ("drops_bias", C.c_int),
         ("drops_fold_const", C.c_int), ("raw_scale", C.c_float),
+        ("sD", C.c_int), ("sH", C.c_int), ("sW", C.c_int),
+        ("out2", C.c_void_p), ("writeback", C.c_int), ("fmt_out", C.c_int),
+        ("ran_conv", C.c_int), ("ran_tx", C.c_int), ("ran_ncb", C.c_int), ("ran_wlds", C.c_int), ("ran_grid", C.c_int),
+        ("ran_items", C.c_int),
+        ("ran_deconv", C.c_int), ("ran_gpw", C.c_int), ("ran_pad", C.c_int),
+        ("ran_norm", C.c_int), ("ran_norm_passes", C.c_int),
     ]
 
 

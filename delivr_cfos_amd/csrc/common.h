@@ -126,6 +126,12 @@ struct dlv_ctx {
     // what the last launches ran, for the layer test hook (dlv_debug_layer16): z-reg instantiation (DLV_DBG_ZR_* bits, 0 = none)
     // and upconv kernel (1 = one tile per workgroup, 2 = persistent, 0 = none)
     int ran_zreg = 0, ran_upconv = 0;
+    // ... and what the launchers of the other families ran (the ran_* fields of dlv_debug_layer_args, include/delivr_hip_diag.h)
+    struct Ran {
+        int conv = -1, tx = 0, ncb = 0, wlds = 0, grid = 0, items = 0;
+        int deconv = -1, gpw = 0, pad = 0;
+        int norm = 0, norm_passes = 0;
+    } ran;
     bool erode_xy_split = false, erode_z_two_sweeps = false, ccl_simple = false;
     bool resample_simple = false, resample_run16 = false;
     int tiff_chunk = 0;      // planes per staging chunk of dlv_tiff_stack_to_device (0: ~256 MB; tests: the double-buffer hand-over on small planes)

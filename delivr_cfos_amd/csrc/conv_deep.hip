@@ -351,6 +351,11 @@ int cd_launch(dlv_ctx* ctx, const void* in1, int c1, const void* in2, int c2, co
     }();
     const unsigned grid = (unsigned)std::min<long long>(nitems, ncu);
     *nparts = ntiles;
+    ctx->ran.conv = DLV_PLAN_DEEP;
+    ctx->ran.tx = TX;
+    ctx->ran.ncb = NCB;
+    ctx->ran.grid = (int)grid;
+    ctx->ran.items = (int)nitems;
     hipLaunchKernelGGL((conv3_deep_kernel<P, TX, NCB>), dim3(grid), dim3(512), C::LDS_BYTES, ctx->stream, (const uint4*)in1, c1 / 8,
                        (const uint4*)in2, c2 / 8, (const uint4*)wpk16, (uint4*)out, partials, cout, D, H, W, tilesY, tilesX, ntiles, B);
     DLV_LAUNCH_CHECK(ctx, "conv3_deep_kernel");
@@ -545,6 +550,8 @@ int dd_launch(dlv_ctx* ctx, const void* in, const void* wpk16, const float* bias
         DLV_HIP(ctx, hipFuncSetAttribute((const void*)deconv2_deep_kernel<P, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         dlv_attr_mark(attr_set, ctx->device);
     }
+    ctx->ran.deconv = DLV_PLAN_DC_DEEP;
+    ctx->ran.gpw = gpw;
     hipLaunchKernelGGL((deconv2_deep_kernel<P, KS>), dim3(dlv_cdiv(vox, 256), G / gpw, B), dim3(512), lds, ctx->stream, (const uint4*)in,
                        (const uint4*)wpk16, bias, (uint4*)out, cout, D, H, W, gpw);
     DLV_LAUNCH_CHECK(ctx, "deconv2_deep_kernel");

@@ -927,6 +927,9 @@ int dlv_conv3_zmarch_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const voi
     const int nseg = dlv_cdiv(D, zseg);
     dim3 grid(tilesY * tilesX, nseg * ncb, B);
     *nparts = tilesY * tilesX * ((D + 15) / 16);
+    ctx->ran.conv = DLV_PLAN_ZMARCH;
+    ctx->ran.ncb = ncb;
+    ctx->ran.grid = (int)(grid.x * grid.y * grid.z);
     // kernel variants (DLV_ZM_VARIANT selects one for A/B timing): VB rows per wave, TYT tile rows -> TYT/VB waves
 #define DLV_ZM_LAUNCH_P(P_, CIN_, VB_, MINW_, TYT_, PIN_, DIST_, ABL_, STAG_)                                                                                  \
     do {                                                                                                                 \

@@ -84,6 +84,7 @@ int dlv_conv3_zreg_launch(dlv_ctx* ctx, bool f16, int cin, int cout, const void*
     a.gx = (unsigned)(tilesY * tilesX); a.gy = (unsigned)(nseg * ncb); a.gz = (unsigned)B;
     ctx->ran_zreg = DLV_DBG_ZR_RAN | (f16 ? DLV_DBG_ZR_F16 : 0) | (cin == 64 ? DLV_DBG_ZR_C64 : 0) | (tyt == 16 ? DLV_DBG_ZR_T16 : 0) |
                     (act ? DLV_DBG_ZR_ACT : 0) | (addend ? DLV_DBG_ZR_ADD : 0);
+    ctx->ran.conv = DLV_PLAN_ZREG;
     if (addend) {
         if (act) {
             if (f16) return tyt == 16 ? dlv_zr_f16_c32_t16_adda1(ctx, a) : dlv_zr_f16_c32_t8_adda1(ctx, a);

@@ -167,6 +167,10 @@ struct Net16 {
             DLV_HIP(ctx, hipFuncSetAttribute((const void*)conv3_mfma_kernel<P, NCB, TX, WLDS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             dlv_attr_mark(attr_done, ctx->device);
         }
+        ctx->ran.conv = DLV_PLAN_GENERIC;
+        ctx->ran.tx = TX;
+        ctx->ran.ncb = NCB;
+        ctx->ran.wlds = WLDS;
         hipLaunchKernelGGL((conv3_mfma_kernel<P, NCB, TX, WLDS>), dim3(dlv_cdiv(d.D, 4) * tY * tX, L.cout / (32 * NCB), B), dim3(256), lds, ctx->stream, in1,
                            c1 / 8, in2, c2 / 8, reinterpret_cast<const uint4*>(wpack<P>(L)), L.bias16, out, partials, L.cout, d.D, d.H, d.W, tY, tX);
         DLV_LAUNCH_CHECK(ctx, "conv3_mfma_kernel");
@@ -222,6 +226,9 @@ struct Net16 {
         constexpr bool seam = !std::is_same<PW, P>::value || !std::is_same<PQ, P>::value;  // (the mixed mode's format change)
         const DlvLabel lb = dlv_label_norm(pooled != nullptr, writeback, P::IS_F16, seam, B, C, d.D, d.H, d.W);
         DlvProf pr(ctx, lb.name, lb.flops, lb.bytes);
+        ctx->ran.norm = DLV_DBG_NM_RAN | (plan.rows ? DLV_DBG_NM_ROWS : 0) | (pooled ? DLV_DBG_NM_POOLED : 0) | (writeback ? DLV_DBG_NM_WRITEBACK : 0) |
+                        (nt ? DLV_DBG_NM_NT : 0) | (seam ? DLV_DBG_NM_SEAM : 0);
+        ++ctx->ran.norm_passes;
         if (plan.rows) {
             const long long items = (long long)(d.D / 2) * (d.H / 2) * (d.W / 64);
             dim3 g2((unsigned)std::max<long long>(1, std::min<long long>((items + 3) / 4, 4096)), C / 8, B);  // (one item per wave: 4 / 8 / 16 items per workgroup 902 / 914 / 939 us)
@@ -266,6 +273,7 @@ struct Net16 {
         const int cout = ctx->deconv[j].cout;
         const DlvLabel lb = dlv_label_pad(P::IS_F16, cout, B, du.vox(), dskip.vox());
         DlvProf pr(ctx, lb.name, lb.flops, lb.bytes);
+        ctx->ran.pad = 1;
         hipLaunchKernelGGL(replicate_pad_cp_kernel, dim3(std::max(1, std::min(grid1d(dskip.vox()), 1024)), B * (cout / 8)), dim3(256), 0, ctx->stream,
                            tmp, out, du.D, du.H, du.W, dskip.D, dskip.H, dskip.W);
         pr.end();
@@ -280,23 +288,28 @@ struct Net16 {
         const long long rowsegs = (long long)din.D * din.H * segs;
         if constexpr (KP <= 4) {
             if (kernel == DLV_PLAN_DC_REGW) {
+                ctx->ran.deconv = DLV_PLAN_DC_REGW;
                 hipLaunchKernelGGL((deconv2_regw_kernel<P, KP>), dim3(dlv_cdiv(rowsegs, 4 * DC_IPW), B), dim3(256), 0, ctx->stream, in, w, L.bias, out, din.D,
                                    din.H, din.W, segs, ssin);
                 return DLV_OK;
             }
         } else {
             if (kernel == DLV_PLAN_DC_WST) {
+                ctx->ran.deconv = DLV_PLAN_DC_WST;
                 hipLaunchKernelGGL((deconv2_wst_kernel<P, KP>), dim3(dlv_cdiv(rowsegs, 4 * DW_IPW), 4 * (L.cout / 32), B), dim3(256), 0, ctx->stream, in, w,
                                    L.bias, out, L.cout, din.D, din.H, din.W, segs, ssin);
                 return DLV_OK;
             }
         }
-        if (kernel == DLV_PLAN_DC_ROWS)
+        if (kernel == DLV_PLAN_DC_ROWS) {
+            ctx->ran.deconv = DLV_PLAN_DC_ROWS;
             hipLaunchKernelGGL((deconv2_rows_kernel<P, KP>), dim3(dlv_cdiv(rowsegs, 4), B), dim3(256), 0, ctx->stream, in, w, L.bias, out, L.cout, din.D, din.H,
                                din.W, segs, ssin);
-        else  // DLV_PLAN_DC_PARITY (no activation on load: the plan made the input final)
+        } else {  // DLV_PLAN_DC_PARITY (no activation on load: the plan made the input final)
+            ctx->ran.deconv = DLV_PLAN_DC_PARITY;
             hipLaunchKernelGGL((deconv2_mfma_kernel<P, KP>), dim3(dlv_cdiv(din.vox(), 128), B), dim3(256), 0, ctx->stream, in, w, L.bias, out, L.cout, din.D,
                                din.H, din.W);
+        }
         return DLV_OK;
     }
 
@@ -320,6 +333,25 @@ struct Net16 {
         }
         pr.end();
         DLV_LAUNCH_CHECK(ctx, "deconv2 kernel");
+        return DLV_OK;
+    }
+
+    // the final 1x1x1 conv on the raw output of the last block (activated on load): plain logits, or (acc) blended into the
+    // accumulator at the windows' places
+    int final_conv(const Act& cur, Dims d, float* logits, float* acc, const int* starts_dev, int flip_dim, int Yp, int Xp, float scale) {
+        if (!cur.ss || cur.C != 32) return dlv_fail(ctx, DLV_ESTATE, "final conv: a raw 32-channel tensor with its scale/shift expected");
+        dim3 grid(std::min(grid1d(d.vox()), 512), B);  // (16 iterations per thread at 128^3 - the software pipeline wants a long loop: 1024 / 512 / 256 workgroups 515 / 487 / 484 us)
+        const DlvLabel lb = dlv_label_final(acc != nullptr, B, d.D, d.H, d.W);
+        DlvProf pr(ctx, lb.name, lb.flops, lb.bytes);
+        if (acc)
+            hipLaunchKernelGGL((final_conv_kernel<P, true>), grid, dim3(256), 0, ctx->stream, cur.p, cur.ss, ctx->final_w,
+                               ctx->final_b, nullptr, starts_dev, flip_dim, Yp, Xp, scale, acc, d.D, d.H, d.W, ctx->blend_w, ctx->blend_min,
+                               ctx->blend_wsum, ctx->range_flag);
+        else
+            hipLaunchKernelGGL((final_conv_kernel<P, false>), grid, dim3(256), 0, ctx->stream, cur.p, cur.ss, ctx->final_w,
+                               ctx->final_b, logits, nullptr, -1, 0, 0, 1.f, nullptr, d.D, d.H, d.W, nullptr, 0.f, nullptr, ctx->range_flag);
+        pr.end();
+        DLV_LAUNCH_CHECK(ctx, "final_conv_kernel");
         return DLV_OK;
     }
 };
@@ -488,20 +520,7 @@ int forward_16(dlv_ctx* ctx, const float* xf, const uint16_t* vol, int Yp, int X
         o.ss = net.ss_of(li + 1);
         cur = o;
     }
-    {
-        dim3 grid(std::min(net.grid1d(dm[0].vox()), 512), B);  // (16 iterations per thread at 128^3 - the software pipeline wants a long loop: 1024 / 512 / 256 workgroups 515 / 487 / 484 us)
-        const DlvLabel lb = dlv_label_final(acc != nullptr, B, d, h, w);
-        DlvProf pr(ctx, lb.name, lb.flops, lb.bytes);
-        if (acc)
-            hipLaunchKernelGGL((final_conv_kernel<P, true>), grid, dim3(256), 0, ctx->stream, cur.p, cur.ss, ctx->final_w,
-                               ctx->final_b, nullptr, starts_dev, flip_dim, Yp, Xp, scale, acc, d, h, w, ctx->blend_w, ctx->blend_min,
-                               ctx->blend_wsum, ctx->range_flag);
-        else
-            hipLaunchKernelGGL((final_conv_kernel<P, false>), grid, dim3(256), 0, ctx->stream, cur.p, cur.ss, ctx->final_w,
-                               ctx->final_b, logits, nullptr, -1, 0, 0, 1.f, nullptr, d, h, w, nullptr, 0.f, nullptr, ctx->range_flag);
-        pr.end();
-        DLV_LAUNCH_CHECK(ctx, "final_conv_kernel");
-    }
+    DLV_TRY(net.final_conv(cur, dm[0], logits, acc, starts_dev, flip_dim, Yp, Xp, scale));
     return DLV_OK;
 }
 
@@ -546,24 +565,94 @@ int debug_layer_16(dlv_ctx* ctx, dlv_debug_layer_args& a) {
     a.ran_zreg = a.ran_upconv = a.ran_stem = a.drops_bias = a.drops_fold_const = 0;
     a.raw_scale = 1.f;
     ctx->ran_zreg = ctx->ran_upconv = 0;
+    ctx->ran = dlv_ctx::Ran{};
+    // what the launchers recorded (the launches are queued by then: host state)
+    const auto report = [&] {
+        const dlv_ctx::Ran& r = ctx->ran;
+        a.ran_zreg = ctx->ran_zreg;
+        a.ran_upconv = ctx->ran_upconv;
+        a.ran_conv = r.conv;
+        a.ran_tx = r.tx;
+        a.ran_ncb = r.ncb;
+        a.ran_wlds = r.wlds;
+        a.ran_grid = r.grid;
+        a.ran_items = r.items;
+        a.ran_deconv = r.deconv;
+        a.ran_gpw = r.gpw;
+        a.ran_pad = r.pad;
+        a.ran_norm = r.norm;
+        a.ran_norm_passes = r.norm_passes;
+    };
+    report();
     if (B < 1 || D < 1 || H < 1 || W < 1) return dlv_fail(ctx, DLV_EINVAL, "debug layer: empty shape");
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int kind = a.kind;
+    if (a.op == DLV_DBG_NORM || a.op == DLV_DBG_FINAL) {
+        const int C = a.c1;
+        const bool fin = a.op == DLV_DBG_FINAL, seam = a.fmt_out != 0;
+        if (!a.in1 || !a.ss1 || C < 8 || C % 8 || (fin && C != 32)) return dlv_fail(ctx, DLV_EINVAL, "norm / final op: raw in1 (C a multiple of 8; final: 32) with ss1");
+        if (fin && (a.out2 || seam)) return dlv_fail(ctx, DLV_EINVAL, "final op: no second output, no format seam");
+        // the two seams of the mixed mode: fp16 raw -> bf16 pooled (the pooling pass 0 -> 1), bf16 raw -> fp16 activated (upcat_1's input)
+        if (seam && (P::IS_F16 ? !a.out2 : a.out2 != nullptr)) return dlv_fail(ctx, DLV_EINVAL, "norm op: the seam is fp16 -> pooled bf16 or bf16 -> activated fp16");
+        if (a.out2 && (D < 2 || H < 2 || W < 2)) return dlv_fail(ctx, DLV_EINVAL, "norm op: nothing to pool");
+        const long long pv = (long long)(D / 2) * (H / 2) * (W / 2);
+        const size_t bx = (size_t)B * C * vox * 2, bq = a.out2 ? (size_t)B * C * pv * 2 : 0;
+        char* base;
+        DLV_TRY(dlv_ws_get(ctx, WS_BF16_ACT, al(bx) + al(bq) + 1024, (void**)&base));
+        uint4 *x = (uint4*)base, *q = a.out2 ? (uint4*)(base + al(bx)) : nullptr;
+        Net16<P> net{ctx, B, nullptr, 0, nullptr};
+        const float2* ss = reinterpret_cast<const float2*>(a.ss1);
+        hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(net.grid1d(vox), C / 8, B), dim3(256), 0, ctx->stream, a.in1, x, C, vox);
+        DLV_LAUNCH_CHECK(ctx, "debug layer: f32_to_cp_kernel");
+        if (fin) {
+            typename Net16<P>::Act cur{x, C, ss};
+            DLV_TRY(net.final_conv(cur, d, a.out, nullptr, nullptr, -1, 0, 0, 1.f));
+            report();
+            return DLV_OK;
+        }
+        const bool wb = q ? a.writeback != 0 : true;
+        bool out_f16 = P::IS_F16, q_f16 = P::IS_F16;
+        if (!seam) DLV_TRY(net.norm_mish(x, C, d, q, ss, wb));
+        else if constexpr (P::IS_F16) {
+            DLV_TRY((net.template norm_mish<P, PBf16>(x, C, d, q, ss, wb)));
+            q_f16 = false;
+        } else {
+            DLV_TRY((net.template norm_mish<PF16, P>(x, C, d, nullptr, ss, true)));
+            out_f16 = true;
+        }
+        report();
+        const dim3 g(net.grid1d(vox), C / 8, B);
+        if (out_f16) hipLaunchKernelGGL(cp_to_f32_kernel<PF16>, g, dim3(256), 0, ctx->stream, x, a.out, C, vox);
+        else hipLaunchKernelGGL(cp_to_f32_kernel<PBf16>, g, dim3(256), 0, ctx->stream, x, a.out, C, vox);
+        if (q) {
+            const dim3 gq(net.grid1d(pv), C / 8, B);
+            if (q_f16) hipLaunchKernelGGL(cp_to_f32_kernel<PF16>, gq, dim3(256), 0, ctx->stream, q, a.out2, C, pv);
+            else hipLaunchKernelGGL(cp_to_f32_kernel<PBf16>, gq, dim3(256), 0, ctx->stream, q, a.out2, C, pv);
+        }
+        DLV_LAUNCH_CHECK(ctx, "debug norm");
+        return DLV_OK;
+    }
     if (kind == 1) {
         if (a.op != DLV_DBG_CONV) return dlv_fail(ctx, DLV_EINVAL, "kind 1 (deconv) runs as op 0 only");
         const int index = a.index, c1 = a.c1;
         if (index < 0 || index >= DLV_N_DECONV) return dlv_fail(ctx, DLV_EINVAL, "deconv index must be 0..3");
         const DlvDeconvLayer& L = ctx->deconv[index];
-        if (!a.in1 || c1 != L.cin || a.c2 != 0 || a.ss1) return dlv_fail(ctx, DLV_EINVAL, "bad channels");
-        const size_t b1 = (size_t)B * c1 * vox * 2, bo = (size_t)B * L.cout * vox * 8 * 2;
+        if (!a.in1 || c1 != L.cin || a.c2 != 0) return dlv_fail(ctx, DLV_EINVAL, "bad channels");
+        const Dims du{2 * D, 2 * H, 2 * W};
+        const Dims dskip = (a.sD | a.sH | a.sW) ? Dims{a.sD, a.sH, a.sW} : du;
+        if (dskip.D < du.D || dskip.D > du.D + 1 || dskip.H < du.H || dskip.H > du.H + 1 || dskip.W < du.W || dskip.W > du.W + 1)
+            return dlv_fail(ctx, DLV_EINVAL, "deconv: each skip dimension is 2 x the input's or one more");
+        const size_t b1 = (size_t)B * c1 * vox * 2, bt = (size_t)B * L.cout * du.vox() * 2, bo = (size_t)B * L.cout * dskip.vox() * 2;
         char* base;
-        DLV_TRY(dlv_ws_get(ctx, WS_BF16_ACT, b1 + bo + 1024, (void**)&base));
-        uint4 *i1 = (uint4*)base, *o = (uint4*)(base + ((b1 + 255) & ~(size_t)255));
+        DLV_TRY(dlv_ws_get(ctx, WS_BF16_ACT, al(b1) + al(bt) + al(bo) + 1024, (void**)&base));
+        uint4 *i1 = (uint4*)base, *tmp = (uint4*)(base + al(b1)), *o = (uint4*)(base + al(b1) + al(bt));
         Net16<P> net{ctx, B, nullptr, 0, nullptr};
         hipLaunchKernelGGL(f32_to_cp_kernel<P>, dim3(net.grid1d(vox), c1 / 8, B), dim3(256), 0, ctx->stream, a.in1, i1, c1, vox);
-        typename Net16<P>::Act t1{i1, c1, nullptr};
-        DLV_TRY(net.deconv(index, t1, o, d));
-        hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(net.grid1d(vox * 8), L.cout / 8, B), dim3(256), 0, ctx->stream, o, a.out,
-                           L.cout, vox * 8);
+        typename Net16<P>::Act t1{i1, c1, reinterpret_cast<const float2*>(a.ss1)};
+        DLV_TRY(net.deconv_to(index, t1, o, tmp, d, dskip));
+        report();
+        hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(net.grid1d(dskip.vox()), L.cout / 8, B), dim3(256), 0, ctx->stream, o, a.out,
+                           L.cout, dskip.vox());
         DLV_LAUNCH_CHECK(ctx, "debug deconv");
         return DLV_OK;
     }
@@ -590,7 +679,6 @@ int debug_layer_16(dlv_ctx* ctx, dlv_debug_layer_args& a) {
         }
     }
     const bool folded = a.op == DLV_DBG_FOLDED;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b1 = (size_t)B * c1 * vox * 2, b2 = (size_t)B * c2 * vox2 * 2, bp = folded ? (size_t)B * 32 * vox * 2 : 0,
                  bo = (size_t)B * L.cout * vox * 2, bst = (size_t)B * 3 * sizeof(int);
     // partial sums: at most one row per 4 x 4 x 8 voxels (generic conv tiles; the z-march / z-reg / stem tiles are larger)
@@ -648,14 +736,14 @@ int debug_layer_16(dlv_ctx* ctx, dlv_debug_layer_args& a) {
         }
         a.raw_scale = exp2f(-(float)L.shift);
     }
-    a.ran_zreg = ctx->ran_zreg;
-    a.ran_upconv = ctx->ran_upconv;
-    a.drops_bias |= a.ran_zreg != 0;  // (the z-reg conv stores no conv bias: the InstanceNorm removes it)
+    report();
+    // (the z-reg conv and conv_deep.hip store no conv bias: the InstanceNorm removes it)
+    a.drops_bias |= a.ran_zreg != 0 || a.ran_conv == DLV_PLAN_DEEP;
     if (kind == 3) {
         DLV_HIP(ctx, hipMemcpyAsync(a.out, net.ss_of(li), (size_t)B * L.cout * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
         return DLV_OK;
     }
-    if (kind == 0 && !final_written) DLV_TRY(net.norm_mish(o, L.cout, d, nullptr, net.ss_of(li), true));
+    if (kind == 0 && !final_written) DLV_TRY(net.norm_mish(o, L.cout, d, nullptr, net.ss_of(li), true));  // (not part of the report)
     hipLaunchKernelGGL(cp_to_f32_kernel<P>, dim3(g, L.cout / 8, B), dim3(256), 0, ctx->stream, o, a.out, L.cout, vox);
     DLV_LAUNCH_CHECK(ctx, "debug layer");
     return DLV_OK;

@@ -393,15 +393,21 @@ class HipEngine:
     _BLOCK_COUT = (0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 5, 5)  # features[] index of each conv block's Cout
 
     def debug_layer16(self, kind: int, op: str = "conv", index: int = 0, in1=None, ss1=None, in2=None, vol=None,
-                      flip_dim=None, precision: str = "bf16"):
+                      flip_dim=None, precision: str = "bf16", skip_shape=None, pool=False, writeback=True, seam=False):
         """test hook (dlv_debug_layer16): one conv block (op "conv", in1 raw where ss1 = its (B, c1, 2) scale/shift is given),
         the folded first conv of upcat_1 (op "folded": in1 fine skip tensor, in2 ACTIVATED coarse tensor) or the stem (op
         "stem": vol = B uint16 windows (B, D, H, W)).  kind 0 final output, 2 raw output, 3 scale/shift (B, Cout, 2).
+        kind 1 (op "conv"): transposed conv `index` of in1 (raw where ss1 is given) -> (B, Cout, 2D, 2H, 2W), or replicate-padded
+        to skip_shape (each dimension 2 x the input's or one more).
+        op "norm": the InstanceNorm + Mish pass over the raw in1 with ss1 -> the tensor as the pass leaves it, or with pool
+        (out, pooled); writeback False: pool only, out stays raw; seam: the mixed mode's format change (fp16: pooled in bf16,
+        needs pool; bf16: activated in fp16, no pool).  op "final": the 1x1x1 conv on the raw in1 (B, 32, D, H, W) with ss1 ->
+        logits (B, D, H, W).
         Returns (out, report): report names the kernels that ran and how the raw output is stored (delivr_hip_diag.h)."""
         torch = self.torch
         a = _lib.DebugLayerArgs()
         a.kind, a.index, a.flip_dim = int(kind), int(index), -1 if flip_dim is None else int(flip_dim)
-        a.op = {"conv": 0, "folded": 1, "stem": 2}[op]
+        a.op = {"conv": 0, "folded": 1, "stem": 2, "norm": 3, "final": 4}[op]
         if op == "stem":
             B, D, H, W = vol.shape
             a.vol = self._dev(vol, torch.uint16, "vol").value
@@ -417,8 +423,26 @@ class HipEngine:
                 a.ss1 = self._dev(ss1, torch.float32, "ss1").value
         if op == "folded":
             a.index = 16
-        cout = self.features[self._BLOCK_COUT[a.index]] if op != "stem" else self.features[0]
-        shape = (B, cout, 2) if kind == 3 else (B, cout, D, H, W)
+        out2 = None
+        if op == "norm":
+            shape = (B, c1, D, H, W)
+            if pool:
+                out2 = torch.empty((B, c1, D // 2, H // 2, W // 2), dtype=torch.float32, device=self.device)
+                a.out2 = self._dev(out2, torch.float32, "out2").value
+            a.writeback, a.fmt_out = int(bool(writeback)), int(bool(seam))
+        elif op == "final":
+            shape = (B, D, H, W)
+        elif kind == 1:
+            if a.index < 0 or a.index >= len(DECONV_BLOCKS):
+                raise ValueError("deconv index must be 0..3")
+            cout = (self.features[4] // 2, self.features[3] // 2, self.features[2] // 2, self.features[1])[a.index]
+            sk = (2 * D, 2 * H, 2 * W) if skip_shape is None else tuple(int(v) for v in skip_shape)
+            if skip_shape is not None:
+                a.sD, a.sH, a.sW = sk
+            shape = (B, cout) + sk
+        else:
+            cout = self.features[self._BLOCK_COUT[a.index]] if op != "stem" else self.features[0]
+            shape = (B, cout, 2) if kind == 3 else (B, cout, D, H, W)
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
         a.out = self._dev(out, torch.float32, "out").value
         a.B, a.D, a.H, a.W = int(B), int(D), int(H), int(W)
@@ -427,6 +451,7 @@ class HipEngine:
         self._check(self.lib.dlv_debug_layer16(self.ctx, C.byref(a)))
         self._leave()
         zr = a.ran_zreg
+        nm = a.ran_norm
         report = {
             "zreg": None if not zr else "{}_c{}_t{}_{}".format("f16" if zr & 2 else "bf16", 64 if zr & 4 else 32, 16 if zr & 8 else 8,
                                                               ("adda1" if zr & 16 else "add") if zr & 32 else ("a1" if zr & 16 else "a0")),
@@ -435,7 +460,19 @@ class HipEngine:
             "drops_bias": bool(a.drops_bias),
             "drops_fold_const": bool(a.drops_fold_const),
             "raw_scale": float(a.raw_scale),
+            # what the launchers recorded: the conv family (a name of _lib.PLAN_CONV_KERNELS) with its template parameters, ...
+            "conv": None if a.ran_conv < 0 else _lib.PLAN_CONV_KERNELS[a.ran_conv],
+            "tx": a.ran_tx, "ncb": a.ran_ncb, "wlds": bool(a.ran_wlds), "grid": a.ran_grid, "items": a.ran_items,
+            # ... the transposed-conv kernel (_lib.PLAN_DECONV_KERNELS), ...
+            "deconv": None if a.ran_deconv < 0 else _lib.PLAN_DECONV_KERNELS[a.ran_deconv],
+            "gpw": a.ran_gpw, "pad": bool(a.ran_pad),
+            # ... and the last normalisation pass before the report was taken (None: none ran)
+            "norm": None if not nm else {"rows": bool(nm & 2), "pooled": bool(nm & 4), "writeback": bool(nm & 8), "nt": bool(nm & 16),
+                                         "seam": bool(nm & 32)},
+            "norm_passes": a.ran_norm_passes,
         }
+        if op == "norm" and pool:
+            return out, out2, report
         return out, report
 
     # ---- sliding window ----------------------------------------------------------------------------

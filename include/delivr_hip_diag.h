@@ -28,10 +28,6 @@ extern "C" {
  * DLV_EINVAL for an unknown name. */
 int dlv_diag_set(dlv_ctx* ctx, const char* name, int value);
 
-/* Runs ONE layer of the bf16 MFMA path on fp32 NCDHW device tensors (converted on the device) so
- * that tests/ can compare each kernel with the oracle in isolation.  kind 0: conv block `index`
- * (1..17: Conv3d k3 + InstanceNorm + Mish) on the channel concatenation [in1 (c1), in2 (c2, may be
- * 0)] -> out (B,Cout,D,H,W); kind 1: ConvTranspose3d `index` (0..3) -> out (B,Cout,2D,2H,2W). */
 /* Diagnostic library only (libdelivr_hip_diag.so, `make diag`): selects an A/B, stamped or timing-only build of the
  * LDS-weights z-marching conv (3/4/6 tile, stagger and streaming-store variants; 20/24 double-buffered half-planes; 40
  * software-pipelined step; 11-13, 30, 41-45 timing-only or stamped builds, profiles/README.md).  The PRODUCT library holds
@@ -52,25 +48,50 @@ int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev
  *   op 0 (DLV_DBG_CONV)   kind 0/2/3: conv block `index` (1..17) on [in1 (c1), in2 (c2)]; ss1 (device float2 [B][c1], may be
  *                         NULL): in1 is RAW and awaits InstanceNorm scale/shift ss1 + Mish - the dispatcher (fuse_layers /
  *                         fuse_levels) decides whether the conv activates it while staging or a normalisation pass runs first.
- *                         kind 1: transposed conv `index` (0..3) of in1 -> (B, Cout, 2D, 2H, 2W).
+ *                         kind 1: transposed conv `index` (0..3) of in1 -> raw output (B, Cout, sD, sH, sW).  With ss1 in1 is RAW:
+ *                         plan_deconv decides between activation on load and a normalisation pass first (ran_norm_passes).
+ *                         sD / sH / sW (all 0: 2D, 2H, 2W): the skip tensor's dimensions, each 2 x the input's or one more -
+ *                         then the output is replicate-padded at the far end as UpCat does (ran_pad).
  *   op 1 (DLV_DBG_FOLDED) the folded first conv of upcat_1 (block 16): in1 = fine skip tensor (B, 32, D, H, W), raw if ss1 is
  *                         given, in2 = ACTIVATED coarse tensor (B, 32, D/2, H/2, W/2); DLV_EUNSUP where a forward would not fold.
  *   op 2 (DLV_DBG_STEM)   block 0 from vol (device uint16 (B, D, H, W): B windows) flipped along flip_dim (2/3/4, -1 none)
  *                         through the MFMA stem (kind 0: statistics pass + activating pass, kind 2/3: raw pass).
+ *   op 3 (DLV_DBG_NORM)   an InstanceNorm + Mish pass over the raw in1 (B, c1, D, H, W) with scale/shift ss1: out = the tensor
+ *                         as the pass leaves it (activated; with out2 and writeback 0: still raw), out2 (may be NULL) = the
+ *                         MaxPool3d(2) of the activated tensor (B, c1, D/2, H/2, W/2).  fmt_out 1: the format seam of the mixed
+ *                         mode - format fp16: the pooled tensor is written in bf16 (out2 required); format bf16: the activated
+ *                         tensor is written in fp16 (no out2).  kind is ignored.
+ *   op 4 (DLV_DBG_FINAL)  the final 1x1x1 conv on the raw in1 (B, 32, D, H, W) with scale/shift ss1 -> fp32 logits (B, D, H, W)
+ *                         (no blending).  kind is ignored.
  * kind 0: final output (B, Cout, D, H, W); 2: raw output in the stored scale (see below); 3: scale/shift pairs (float2 [B][Cout]).
  * Reported: ran_zreg (DLV_DBG_ZR_* bits of the z-reg instantiation that ran, 0: another kernel), ran_upconv (1 one tile per
  * workgroup, 2 persistent, 0 none), ran_stem (1: stem_mfma_kernel), and how the raw output relates to conv3d + bias:
  *   raw = raw_scale * (conv3d(x, W) + (drops_bias ? 0 : bias) - (drops_fold_const ? sum_taps W_up * bias_up : 0))
- * raw_scale = 2^-shift of the block (dlv_unet_set_conv_shift), times STEM_SCALE (2^-8 in fp16) for the stem. */
+ * raw_scale = 2^-shift of the block (dlv_unet_set_conv_shift), times STEM_SCALE (2^-8 in fp16) for the stem.
+ * What the launchers of the other families ran (recorded at the launch sites, not read from the plan):
+ *   ran_conv    DLV_PLAN_ZREG / DEEP / ZMARCH / GENERIC of the conv launch, -1: none; with it ran_tx / ran_ncb (DEEP, GENERIC: the
+ *               template parameters; ZMARCH: cout blocks), ran_wlds (GENERIC), ran_grid (workgroups; DEEP, ZMARCH) and ran_items
+ *               (DEEP: work items the persistent workgroups walk)
+ *   ran_deconv  DLV_PLAN_DC_* of the transposed-conv launch, -1: none; ran_gpw: 64-channel groups per workgroup (DC_DEEP);
+ *               ran_pad: replicate_pad_cp_kernel ran
+ *   ran_norm    of the LAST normalisation pass: DLV_DBG_NM_* bits (0: none ran); ran_norm_passes: how many ran */
 #define DLV_DBG_CONV 0
 #define DLV_DBG_FOLDED 1
 #define DLV_DBG_STEM 2
+#define DLV_DBG_NORM 3
+#define DLV_DBG_FINAL 4
 #define DLV_DBG_ZR_RAN 1
 #define DLV_DBG_ZR_F16 2
 #define DLV_DBG_ZR_C64 4
 #define DLV_DBG_ZR_T16 8
 #define DLV_DBG_ZR_ACT 16
 #define DLV_DBG_ZR_ADD 32
+#define DLV_DBG_NM_RAN 1
+#define DLV_DBG_NM_ROWS 2      /* norm_mish_pool_rows_kernel (else norm_mish_kernel) */
+#define DLV_DBG_NM_POOLED 4
+#define DLV_DBG_NM_WRITEBACK 8
+#define DLV_DBG_NM_NT 16       /* non-temporal instantiation */
+#define DLV_DBG_NM_SEAM 32     /* written-back or pooled tensor in the other 16-bit format */
 typedef struct dlv_debug_layer_args {
     int kind, op, index;
     const float* in1;
@@ -85,6 +106,14 @@ typedef struct dlv_debug_layer_args {
     /* reported */
     int ran_zreg, ran_upconv, ran_stem, drops_bias, drops_fold_const;
     float raw_scale;
+    /* further inputs (0 / NULL: as before) */
+    int sD, sH, sW;
+    float* out2;
+    int writeback, fmt_out;
+    /* reported */
+    int ran_conv, ran_tx, ran_ncb, ran_wlds, ran_grid, ran_items;
+    int ran_deconv, ran_gpw, ran_pad;
+    int ran_norm, ran_norm_passes;
 } dlv_debug_layer_args;
 int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args);
 

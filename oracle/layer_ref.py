@@ -1,11 +1,12 @@
-"""float64 references of single layers of the 16-bit MFMA path (tests/test_gpu_conv_kernels.py).
+"""float64 references of single layers of the 16-bit MFMA path (tests/test_gpu_conv_kernels.py, tests/test_gpu_layer_kernels.py).
 
 TEST INFRASTRUCTURE ONLY, like the rest of ``oracle/``.  Each reference works on the operands the kernel receives - inputs
 and weights rounded to the 16-bit format with torch's ``.half()`` / ``.bfloat16()`` - and does the arithmetic in float64 on
 the CPU.  ``fmt=None`` skips the rounding: then the references equal the oracle U-Net's own layers run in float64
 (tests/test_layer_ref_cpu.py).
 
-Every reference returns a dict:
+Every conv-block reference returns a dict (the references of the layers without an InstanceNorm of their own - deconv,
+norm_pool, replicate_pad, final_logits - say what they return):
   raw    conv output including every bias term (what torch's modules compute)
   drop   the per-channel constant (B, C) a kernel may leave out of its stored raw output: the conv bias (z-reg conv) or the
          folded conv's interior up-sampling bias term  sum_taps Wc_up * b_up  (upconv.hip); see ``stored_raw``
@@ -104,3 +105,57 @@ def stem(vol, weight, bias, gamma, beta, fmt: Optional[str], w_scale: float = 1.
     raw = (F.conv3d(lo, round16(w * w_scale, fmt), padding=1) + F.conv3d(hi, round16(256.0 * w * w_scale, fmt), padding=1)) / w_scale
     raw = raw + bias.double()[None, :, None, None, None]
     return _norm(raw, gamma, beta, bias.double()[None, :].expand(raw.shape[0], -1))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the other layers of the 16-bit forward (tests/test_gpu_layer_kernels.py): no InstanceNorm of their own, so each returns what
+# its check needs instead of the dict above
+# ---------------------------------------------------------------------------------------------------
+def deconv(x, w, b, fmt: Optional[str], ss=None):
+    """ConvTranspose3d(k2, s2) of x (B, Cin, D, H, W) with w (Cin, Cout, 2, 2, 2) and bias b.  ss (B, Cin, 2): x is raw and goes
+    through ``activate`` first.  Returns {"raw": the output with its bias, "x": the operand the kernel multiplies, "abs": the
+    same transposed conv of |x| and |w| without bias (the sum of absolute products the fp32 accumulation error scales with)}."""
+    import torch.nn.functional as F
+
+    a = activate(x, ss, fmt) if ss is not None else round16(x, fmt)
+    w16 = round16(w, fmt)
+    return {"raw": F.conv_transpose3d(a, w16, b.double(), stride=2), "x": a, "abs": F.conv_transpose3d(a.abs(), w16.abs(), None, stride=2)}
+
+
+def norm_pool(raw, ss, fmt: Optional[str], fmt_out: Optional[str], pool: bool):
+    """The InstanceNorm + Mish pass over a stored raw tensor: y = round16(raw, fmt) * sc + sh, act = mish(y).  Returns {"y", "act"
+    (both unrounded float64), "out": round16(act, fmt_out), and with pool "pooled_act": MaxPool3d(2) of act (odd sizes drop the
+    last plane / row / column) and "pooled": round16 of it to fmt_out (rounding is monotone: the maximum of the rounded values)}."""
+    import torch.nn.functional as F
+
+    s = ss.double()
+    y = round16(raw, fmt) * s[:, :, 0, None, None, None] + s[:, :, 1, None, None, None]
+    act = mish(y)
+    r = {"y": y, "act": act, "out": round16(act, fmt_out)}
+    if pool:
+        r["pooled_act"] = F.max_pool3d(act, 2)
+        r["pooled"] = round16(r["pooled_act"], fmt_out)
+    return r
+
+
+def replicate_pad(u, skip_shape):
+    """UpCat's padding of an up-sampled tensor to the skip tensor's (D, H, W): the edge value once more at the far end of every
+    dimension that is a voxel short."""
+    import torch.nn.functional as F
+
+    pad = []
+    for have, want in zip(reversed(u.shape[2:]), reversed(tuple(skip_shape))):
+        if want - have not in (0, 1):
+            raise ValueError(f"skip shape {tuple(skip_shape)} against {tuple(u.shape[2:])}")
+        pad += [0, want - have]
+    return F.pad(u, pad, mode="replicate") if any(pad) else u
+
+
+def final_logits(raw, ss, w, b, fmt: Optional[str]):
+    """The final Conv3d(32 -> 1, k1) on the raw output of the last block, activated on load in fp32 (no 16-bit rounding of the
+    activation; w (1, 32, 1, 1, 1) and b stay fp32).  Returns {"logits" (B, D, H, W), "y", "m" = mish(y)} (B, 32, D, H, W)."""
+    s = ss.double()
+    y = round16(raw, fmt) * s[:, :, 0, None, None, None] + s[:, :, 1, None, None, None]
+    m = mish(y)
+    wc = w.double().reshape(1, -1, 1, 1, 1)
+    return {"logits": (m * wc).sum(dim=1) + b.double().reshape(()), "y": y, "m": m}

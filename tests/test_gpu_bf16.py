@@ -39,27 +39,31 @@ def _conv_block(net, li):
     return mod
 
 
-# (layer, c1, c2, D, H, W): covers NCB 1/2/4, TX 16/8, concat inputs, ragged tile borders
+# (layer, c1, c2, D, H, W); CONV_FAMILY: the conv family the dispatcher (csrc/layer_plan.h) sends each case to under the default
+# switches, asserted from the layer hook's report.  W < 32 at these sizes: conv_deep.hip (16-wide and 8-wide tiles, 32 / 64
+# output channels per workgroup, concat inputs, ragged tile borders); W >= 32: the z-march up to 32768 voxels, the z-reg conv
+# above.  None of them reaches the generic conv (conv3_mfma_kernel): each kernel on its own, with every instantiation, is in
+# tests/test_gpu_layer_kernels.py and tests/test_gpu_conv_kernels.py
 CONV_CASES = [
     (1, 32, 0, 8, 8, 32),
-    (1, 32, 0, 6, 10, 24),     # partial tiles in z, y and x
-    (16, 32, 32, 8, 12, 16),   # concat 32+32 -> 32
-    (5, 64, 0, 8, 8, 16),      # 64 -> 64 (NCB 2)
-    (4, 32, 0, 4, 6, 8),       # 32 -> 64, W=8 -> TX 8
-    (9, 256, 0, 4, 4, 8),      # 256 -> 256 (NCB 4), TX 8
-    (10, 128, 128, 2, 6, 12),  # concat 128+128 -> 128, odd sizes
+    (1, 32, 0, 6, 10, 24),      # partial tiles in z, y and x
+    (16, 32, 32, 8, 12, 16),    # concat 32+32 -> 32
+    (5, 64, 0, 8, 8, 16),       # 64 -> 64
+    (4, 32, 0, 4, 6, 8),        # 32 -> 64, W=8 -> 8-wide tiles
+    (9, 256, 0, 4, 4, 8),       # 256 -> 256, 8-wide tiles
+    (10, 128, 128, 2, 6, 12),   # concat 128+128 -> 128, odd sizes
     (12, 64, 64, 4, 8, 16),
     # W >= 32 and Cout = 32 (ragged tiles, z segments, concat).  Layers of at most 32768 voxels take the LDS-weights
-    # z-march (conv_zmarch.hip), larger ones the register-resident-weights conv (conv_zreg_kernel.h, 8-row tiles here;
-    # every instantiation of it: tests/test_gpu_conv_kernels.py)
-    (1, 32, 0, 6, 12, 40),     # conv_zmarch.hip
-    (17, 32, 0, 40, 16, 64),   # z-reg c32_t8
-    (16, 32, 32, 9, 8, 32),    # conv_zmarch.hip
-    (14, 32, 32, 24, 20, 72),  # z-reg c64_t8 (32 + 32)
+    # z-march (conv_zmarch.hip), larger ones the register-resident-weights conv (conv_zreg_kernel.h, 8-row tiles here)
+    (1, 32, 0, 6, 12, 40),
+    (17, 32, 0, 40, 16, 64),     # c32_t8
+    (16, 32, 32, 9, 8, 32),
+    (14, 32, 32, 24, 20, 72),    # c64_t8 (32 + 32)
     # Cout = 64 with W >= 32: two output-channel blocks (z segments, ragged rows)
-    (4, 32, 0, 20, 12, 32),    # conv_zmarch.hip
-    (5, 64, 0, 33, 24, 64),    # z-reg c64_t8
+    (4, 32, 0, 20, 12, 32),
+    (5, 64, 0, 33, 24, 64),      # c64_t8
 ]
+CONV_FAMILY = dict(zip(CONV_CASES, ("ZMARCH", "DEEP", "DEEP", "DEEP", "DEEP", "DEEP", "DEEP", "DEEP", "ZMARCH", "ZREG", "ZMARCH", "ZREG", "ZMARCH", "ZREG")))
 
 
 @pytest.mark.parametrize("li,c1,c2,D,H,W", CONV_CASES)
@@ -79,8 +83,9 @@ def test_conv_block_bf16(eng, net, li, c1, c2, D, H, W):
     with torch.no_grad():
         raw = F.conv3d(xin, _bf(blk.conv.weight), blk.conv.bias, padding=1)
         ref = F.mish(F.instance_norm(raw, weight=blk.adn.N.weight, bias=blk.adn.N.bias, eps=1e-5))
-    out = eng.debug_layer_bf16(0, li, x1.cuda(), None if x2 is None else x2.cuda()).cpu()
-    err = (out - ref).abs()
+    out, rep = eng.debug_layer16(0, "conv", li, x1.cuda(), None, None if x2 is None else x2.cuda(), precision="bf16")
+    assert rep["conv"] == CONV_FAMILY[(li, c1, c2, D, H, W)], rep
+    err = (out.cpu() - ref).abs()
     assert err.max() < 0.06, float(err.max())
     assert err.mean() < 6e-3, float(err.mean())
 
@@ -95,8 +100,10 @@ def test_deconv_bf16(eng, net, j, D, H, W):
     x = _bf(torch.randn((2, up.in_channels, D, H, W), generator=g))
     with torch.no_grad():
         ref = F.conv_transpose3d(x, _bf(up.weight), up.bias, stride=2)
-    out = eng.debug_layer_bf16(1, j, x.cuda()).cpu()
-    err = (out - ref).abs()
+    out, rep = eng.debug_layer16(1, "conv", j, x.cuda(), precision="bf16")
+    assert rep["deconv"] == ("DEEP" if j < 2 else "ROWS"), rep
+    assert tuple(out.shape) == tuple(ref.shape)
+    err = (out.cpu() - ref).abs()
     scale = float(ref.abs().max())
     assert err.max() < 8e-3 * max(scale, 1.0), (float(err.max()), scale)
 
@@ -218,8 +225,9 @@ def test_conv_block_fp16(eng, net, li, c1, c2, D, H, W):
     with torch.no_grad():
         raw = F.conv3d(xin, blk.conv.weight.half().float(), blk.conv.bias, padding=1)
         ref = F.mish(F.instance_norm(raw, weight=blk.adn.N.weight, bias=blk.adn.N.bias, eps=1e-5))
-    out = eng.debug_layer_bf16(0, li, x1.cuda(), None if x2 is None else x2.cuda(), precision="fp16").cpu()
-    err = (out - ref).abs()
+    out, rep = eng.debug_layer16(0, "conv", li, x1.cuda(), None, None if x2 is None else x2.cuda(), precision="fp16")
+    assert rep["conv"] == CONV_FAMILY[(li, c1, c2, D, H, W)], rep
+    err = (out.cpu() - ref).abs()
     assert err.max() < 0.01, float(err.max())
     assert err.mean() < 1e-3, float(err.mean())
 

@@ -127,6 +127,12 @@ class LayerPlan(C.Structure):
                 ("bytes", C.c_double * PLAN_MAX_LABELS)]
 
 
+class CclRan(C.Structure):
+    """dlv_ccl_ran (include/delivr_hip_diag.h): what the last dlv_ccl26_dev of a context launched."""
+    _fields_ = [("aligned", C.c_int), ("merge_rows", C.c_int), ("relabel", C.c_int), ("init_grid", C.c_int),
+                ("init_per", C.c_uint64), ("blocks", C.c_uint64), ("groups", C.c_uint64), ("list_n", C.c_uint64)]
+
+
 class SwParams(C.Structure):
     _fields_ = [
         ("Zp", C.c_int), ("Yp", C.c_int), ("Xp", C.c_int),
@@ -237,6 +243,7 @@ SIGNATURES = {
     "dlv_tiff_stack_to_device": (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_longlong,
                                             C.c_longlong, C.c_int]),
     "dlv_diag_set": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "dlv_diag_ccl_ran": (C.c_int, [_P, C.POINTER(CclRan)]),
     "dlv_diag_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.POINTER(LayerPlan)]),
     "dlv_cells_csv": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -662,10 +662,18 @@ int dlv_diag_set(dlv_ctx* ctx, const char* name, int value) {
     else if (n == "erode_xy_split") ctx->erode_xy_split = value != 0;
     else if (n == "erode_z_two_sweeps") ctx->erode_z_two_sweeps = value != 0;
     else if (n == "ccl_simple") ctx->ccl_simple = value != 0;
+    else if (n == "ccl_init_grid") ctx->ccl_init_grid = value > 0 ? value : 0;
     else if (n == "resample_simple") ctx->resample_simple = value != 0;
     else if (n == "resample_run16") ctx->resample_run16 = value != 0;
     else if (n == "tiff_chunk") ctx->tiff_chunk = value > 0 ? value : 0;
     else return dlv_fail(ctx, DLV_EINVAL, "dlv_diag_set: unknown switch '%s'", name);
+    return DLV_OK;
+}
+
+// what the last dlv_ccl26_dev of this context launched (ccl.hip records it at the launch sites)
+int dlv_diag_ccl_ran(dlv_ctx* ctx, dlv_ccl_ran* out) {
+    if (!ctx || !out) return DLV_EINVAL;
+    *out = ctx->ccl_ran;
     return DLV_OK;
 }
 

@@ -63,6 +63,10 @@ __device__ __forceinline__ unsigned mask_bits16(const uint8_t* __restrict__ mask
     return bits;
 }
 
+// chunks per workgroup of ccl_init_kernel: whole iterations of its 256 threads.  The kernel and the launch record of
+// dlv_ccl26_dev (dlv_diag_ccl_ran) ask the same function
+__host__ __device__ __forceinline__ u64 ccl_init_per(u64 nch, u64 grid) { return ((nch + grid - 1) / grid + 255) / 256 * 256; }
+
 // parents of the foreground voxels only (the background entries of L are never read: 17 GB of writes less on a
 // 2^32-voxel volume)
 // ... and the BIT MASK of the volume (one uint16 per 16 voxels): the only pass that reads the byte mask.  Every later
@@ -79,7 +83,7 @@ __global__ void __launch_bounds__(256) ccl_init_kernel(const uint8_t* __restrict
     __shared__ u32 fill, gbase;
     const u64 nch = (n + 15) / 16;
     const int lane = threadIdx.x & 63;
-    const u64 per = ((nch + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
+    const u64 per = ccl_init_per(nch, gridDim.x);
     const u64 cb = (u64)blockIdx.x * per, ce = min(cb + per, nch);
     if (threadIdx.x == 0) fill = 0;
     __syncthreads();
@@ -578,8 +582,10 @@ int ccl_number_roots(dlv_ctx* ctx, const CclWs& w, u32* labels, u64 n) {
     return DLV_OK;
 }
 
-// every voxel of the volume is written: 0 for the background, the root's label for the rest
-int ccl_relabel_whole(dlv_ctx* ctx, const CclWs& w, u32* labels, u64 n, bool aligned) {
+// every voxel of the volume is written: 0 for the background, the root's label for the rest.  ran (may be null): receives the
+// kernel launched, in the numbering of dlv_ccl_ran.relabel
+int ccl_relabel_whole(dlv_ctx* ctx, const CclWs& w, u32* labels, u64 n, bool aligned, int* ran = nullptr) {
+    if (ran) *ran = aligned ? 1 : 2;  // (lines : chunks - the two launches below)
     if (aligned)
         hipLaunchKernelGGL(ccl_relabel_lines_kernel, dim3((unsigned)std::min<u64>((n / 1024 + 3) / 4 + 1, (u64)256 * 32)), dim3(256), 0,
                            ctx->stream, w.bm, w.rb, n, labels);
@@ -622,7 +628,8 @@ int dlv_ccl26_dev(dlv_ctx* ctx, const uint8_t* mask_dev, int Z, int Y, int X, ui
     CclWs w;
     DLV_TRY(ccl_ws_get(ctx, n, w));
     u32* L = labels_dev;
-    const int gs = (int)std::min<u64>((w.nch + 255) / 256, (u64)256 * 64);
+    int gs = (int)std::min<u64>((w.nch + 255) / 256, (u64)256 * 64);
+    if (ctx->ccl_init_grid > 0) gs = std::min(gs, ctx->ccl_init_grid);  // (dlv_diag_set "ccl_init_grid": tests of the mid-loop flush)
     // 16-byte accesses need the mask 16-byte and the labels 16-byte aligned (hipMalloc / torch allocations are)
     const bool aligned = ((reinterpret_cast<uintptr_t>(mask_dev) | reinterpret_cast<uintptr_t>(labels_dev)) & 15) == 0;
     // bytes: the byte mask is read once (1 B), its bit mask written once and scanned by five kernels (6/8 B), the labels are
@@ -633,8 +640,16 @@ int dlv_ccl26_dev(dlv_ctx* ctx, const uint8_t* mask_dev, int Z, int Y, int X, ui
     if (!simple) DLV_HIP(ctx, hipMemsetAsync(labels_dev, 0, (size_t)n * 4, ctx->stream));
     hipLaunchKernelGGL(ccl_init_kernel, dim3(gs), dim3(256), 0, ctx->stream, mask_dev, L, n, aligned, w.bm, w.list, w.list_n);
     DLV_LAUNCH_CHECK(ctx, "ccl_init_kernel");
+    dlv_ccl_ran& ran = ctx->ccl_ran;  // what this call launches (dlv_diag_ccl_ran): written at the launch sites
+    ran = dlv_ccl_ran();
+    ran.aligned = aligned ? 1 : 0;
+    ran.init_grid = gs;
+    ran.init_per = ccl_init_per(w.nch, (u64)gs);
+    ran.blocks = w.nb;
+    ran.groups = (w.nb + SGRP - 1) / SGRP;
     const int gl = 256 * 16;  // list kernels: grid-stride over the device-side count
-    if (aligned && X % 16 == 0)
+    ran.merge_rows = (aligned && X % 16 == 0) ? 1 : 0;
+    if (ran.merge_rows)
         hipLaunchKernelGGL(ccl_merge_list_kernel<true>, dim3(gl), dim3(256), 0, ctx->stream, w.bm, L, Y, X, w.list, w.list_n);
     else
         hipLaunchKernelGGL(ccl_merge_list_kernel<false>, dim3(gl), dim3(256), 0, ctx->stream, w.bm, L, Y, X, w.list, w.list_n);
@@ -642,15 +657,19 @@ int dlv_ccl26_dev(dlv_ctx* ctx, const uint8_t* mask_dev, int Z, int Y, int X, ui
     hipLaunchKernelGGL(ccl_compress_kernel, dim3(gl), dim3(256), 0, ctx->stream, w.bm, L, w.list, w.list_n);
     DLV_LAUNCH_CHECK(ctx, "ccl_compress_kernel");
     DLV_TRY(ccl_number_roots(ctx, w, labels_dev, n));
-    if (!simple)
+    if (!simple) {
+        ran.relabel = 0;
         hipLaunchKernelGGL(ccl_relabel_list_kernel, dim3(gl), dim3(256), 0, ctx->stream, w.bm, w.rb, n, labels_dev, w.list, w.list_n, aligned);
-    else
-        DLV_TRY(ccl_relabel_whole(ctx, w, labels_dev, n, aligned));
+    } else {
+        DLV_TRY(ccl_relabel_whole(ctx, w, labels_dev, n, aligned, &ran.relabel));
+    }
     DLV_LAUNCH_CHECK(ctx, "ccl_relabel_kernel");
     pr.end();
-    u32 total = 0;
+    u32 total = 0, listed = 0;
     DLV_HIP(ctx, hipMemcpyAsync(&total, w.counts + w.nb, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DLV_HIP(ctx, hipMemcpyAsync(&listed, w.list_n, 4, hipMemcpyDeviceToHost, ctx->stream));  // (the launch record's list_n)
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ran.list_n = listed;
     *n_out = total;
     return DLV_OK;
 }

@@ -607,6 +607,12 @@ class HipEngine:
         self._leave()
         return labels, int(n.value)
 
+    def ccl_ran(self) -> dict:
+        """what the last dlv_ccl26_dev of this context launched (include/delivr_hip_diag.h: dlv_ccl_ran) - tests"""
+        out = _lib.CclRan()
+        self._check(self.lib.dlv_diag_ccl_ran(self.ctx, C.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in out._fields_}
+
     def cc_stats(self, labels, n: int) -> dict:
         """cc3d.statistics(no_slice_conversion=True) layout (count_blobs.py:85)."""
         Z, Y, X = (int(v) for v in labels.shape)

@@ -23,10 +23,26 @@ extern "C" {
  *   "pool_rows_off" 1     the pooling pass by pooled voxels instead of by full lines
  *   "erode_xy_split" 1, "erode_z_two_sweeps" 1, "ccl_simple" 1, "resample_simple" 1, "resample_run16" 1
  *                         the earlier kernels of finalize / CCL / the resamplers (cross-checks in tests/test_gpu_parity.py)
+ *   "ccl_init_grid" n     at most n workgroups for ccl_init_kernel (0: its own choice): a workgroup that owns 2048 chunks or more
+ *                         flushes its chunk buffer inside its loop (tests/test_gpu_ccl_kernels.py); no other kernel, same labels
  *   "tiff_chunk" n        planes per pinned staging chunk of dlv_tiff_stack_to_device (0: ~256 MB): the hand-over between the two
  *                         staging buffers on stacks of small planes (tests/test_gpu_pipeline.py)
  * DLV_EINVAL for an unknown name. */
 int dlv_diag_set(dlv_ctx* ctx, const char* name, int value);
+
+/* What the last dlv_ccl26_dev of this context launched, recorded at its launch sites:
+ *   aligned      mask and labels both start on a 16-byte boundary (16-byte loads and stores)
+ *   merge_rows   1: ccl_merge_list_kernel<true> (row windows; aligned and X % 16 == 0), 0: the per-voxel merge
+ *   relabel      0: ccl_relabel_list_kernel (memset + listed chunks), 1: ccl_relabel_lines_kernel, 2: ccl_relabel_kernel ("ccl_simple")
+ *   init_grid    workgroups of ccl_init_kernel, init_per: the 16-voxel chunks each of them owns (a multiple of 256)
+ *   blocks       4096-voxel blocks of the renumbering, groups: the 1024-block groups of its two-level scan
+ *   list_n       chunks with foreground that ccl_init_kernel listed (read back with the number of labels)
+ * All 0 before the first labelling. */
+typedef struct dlv_ccl_ran {
+    int aligned, merge_rows, relabel, init_grid;
+    uint64_t init_per, blocks, groups, list_n;
+} dlv_ccl_ran;
+int dlv_diag_ccl_ran(dlv_ctx* ctx, dlv_ccl_ran* out);
 
 /* Diagnostic library only (libdelivr_hip_diag.so, `make diag`): selects an A/B, stamped or timing-only build of the
  * LDS-weights z-marching conv (3/4/6 tile, stagger and streaming-store variants; 20/24 double-buffered half-planes; 40

@@ -97,6 +97,8 @@ class DebugLayerArgs(C.Structure):
         ("ran_items", C.c_int),
         ("ran_deconv", C.c_int), ("ran_gpw", C.c_int), ("ran_pad", C.c_int),
         ("ran_norm", C.c_int), ("ran_norm_passes", C.c_int),
+        ("starts", C.POINTER(C.c_int)), ("acc", C.c_void_p), ("Yp", C.c_int), ("Xp", C.c_int), ("scale", C.c_float),
+        ("bw", C.c_void_p), ("bmin", C.c_float), ("wsum", C.c_void_p),
     ]
 
 

@@ -606,7 +606,37 @@ int debug_layer_16(dlv_ctx* ctx, dlv_debug_layer_args& a) {
         DLV_LAUNCH_CHECK(ctx, "debug layer: f32_to_cp_kernel");
         if (fin) {
             typename Net16<P>::Act cur{x, C, ss};
-            DLV_TRY(net.final_conv(cur, d, a.out, nullptr, nullptr, -1, 0, 0, 1.f));
+            if (!a.acc) {
+                DLV_TRY(net.final_conv(cur, d, a.out, nullptr, nullptr, -1, 0, 0, 1.f));
+                report();
+                return DLV_OK;
+            }
+            // the blend instantiation, as a pass launches it: B windows at `starts` of an accumulator of Yp x Xp planes
+            const float scale = a.scale != 0.f ? a.scale : 1.f;
+            if (!a.starts) return dlv_fail(ctx, DLV_EINVAL, "final op (blend): the windows' starts expected");
+            if (!(a.flip_dim == -1 || (a.flip_dim >= 2 && a.flip_dim <= 4))) return dlv_fail(ctx, DLV_EINVAL, "final op (blend): flip_dim must be -1, 2, 3 or 4");
+            if (!(fabsf(scale) <= 3.0e38f) || !(a.bmin >= 0.f && a.bmin <= 3.0e38f)) return dlv_fail(ctx, DLV_EINVAL, "final op (blend): scale and bmin must be finite, bmin >= 0");
+            if (a.wsum && !a.bw) return dlv_fail(ctx, DLV_EINVAL, "final op (blend): wsum collects the factors bw");
+            for (int n = 0; n < B; ++n) {
+                const int z0 = a.starts[3 * n], y0 = a.starts[3 * n + 1], x0 = a.starts[3 * n + 2];
+                if (z0 < 0 || y0 < 0 || x0 < 0 || (long long)y0 + H > a.Yp || (long long)x0 + W > a.Xp)
+                    return dlv_fail(ctx, DLV_EINVAL, "final op (blend): window %d at (%d, %d, %d) leaves the %d x %d planes", n, z0, y0, x0, a.Yp, a.Xp);
+            }
+            int* starts_dev;
+            DLV_TRY(dlv_ws_get(ctx, WS_TILE_META, (size_t)B * 3 * sizeof(int), (void**)&starts_dev));
+            DLV_HIP(ctx, hipMemcpyAsync(starts_dev, a.starts, (size_t)B * 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's array)
+            const float* keep_w = ctx->blend_w;
+            const float keep_min = ctx->blend_min;
+            float* keep_wsum = ctx->blend_wsum;
+            ctx->blend_w = a.bw;
+            ctx->blend_min = a.bmin;
+            ctx->blend_wsum = a.wsum;
+            const int rc = net.final_conv(cur, d, nullptr, a.acc, starts_dev, a.flip_dim, a.Yp, a.Xp, scale);
+            ctx->blend_w = keep_w;
+            ctx->blend_min = keep_min;
+            ctx->blend_wsum = keep_wsum;
+            DLV_TRY(rc);
             report();
             return DLV_OK;
         }
@@ -819,7 +849,7 @@ int dlv_unet_tiles_bf16(dlv_ctx* ctx, const uint16_t* vol, int Yp, int Xp, const
 // test hooks (include/delivr_hip_diag.h): one layer of the 16-bit path on fp32 NCDHW tensors (converted on the device) in the
 // format of dlv_debug_set_format.  dlv_debug_layer_bf16 is the older positional form of dlv_debug_layer16.
 extern "C" int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args) {
-    if (!ctx || !args || !args->out) return DLV_EINVAL;
+    if (!ctx || !args || (!args->out && !(args->op == DLV_DBG_FINAL && args->acc))) return DLV_EINVAL;  // (the blend writes no `out`)
     if (!ctx->weights_loaded) return dlv_fail(ctx, DLV_ESTATE, "no weights");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->debug_f16) return debug_layer_16<PF16>(ctx, *args);

@@ -393,7 +393,8 @@ class HipEngine:
     _BLOCK_COUT = (0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 5, 5)  # features[] index of each conv block's Cout
 
     def debug_layer16(self, kind: int, op: str = "conv", index: int = 0, in1=None, ss1=None, in2=None, vol=None,
-                      flip_dim=None, precision: str = "bf16", skip_shape=None, pool=False, writeback=True, seam=False):
+                      flip_dim=None, precision: str = "bf16", skip_shape=None, pool=False, writeback=True, seam=False,
+                      acc=None, starts=None, scale: float = 1.0, bw=None, bmin: float = 0.0, wsum=None):
         """test hook (dlv_debug_layer16): one conv block (op "conv", in1 raw where ss1 = its (B, c1, 2) scale/shift is given),
         the folded first conv of upcat_1 (op "folded": in1 fine skip tensor, in2 ACTIVATED coarse tensor) or the stem (op
         "stem": vol = B uint16 windows (B, D, H, W)).  kind 0 final output, 2 raw output, 3 scale/shift (B, Cout, 2).
@@ -402,7 +403,9 @@ class HipEngine:
         op "norm": the InstanceNorm + Mish pass over the raw in1 with ss1 -> the tensor as the pass leaves it, or with pool
         (out, pooled); writeback False: pool only, out stays raw; seam: the mixed mode's format change (fp16: pooled in bf16,
         needs pool; bf16: activated in fp16, no pool).  op "final": the 1x1x1 conv on the raw in1 (B, 32, D, H, W) with ss1 ->
-        logits (B, D, H, W).
+        logits (B, D, H, W).  op "final" with acc (fp32 (Z, Yp, Xp)): the blend mode - the B windows, forwarded flipped along
+        flip_dim, are un-flipped and added into acc at starts (B, 3) times `scale`, or with bw (fp32, D + H + W factors) times
+        max(bw[z] bw[D + y] bw[D + H + x], bmin) * scale, which wsum (shaped like acc, optional) collects; returns the report alone.
         Returns (out, report): report names the kernels that ran and how the raw output is stored (delivr_hip_diag.h)."""
         torch = self.torch
         a = _lib.DebugLayerArgs()
@@ -443,8 +446,30 @@ class HipEngine:
         else:
             cout = self.features[self._BLOCK_COUT[a.index]] if op != "stem" else self.features[0]
             shape = (B, cout, 2) if kind == 3 else (B, cout, D, H, W)
-        out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        a.out = self._dev(out, torch.float32, "out").value
+        blend = acc is not None
+        if blend:
+            if op != "final":
+                raise ValueError("acc: the blend mode belongs to op 'final'")
+            st = np.ascontiguousarray(starts, dtype=np.intc)
+            if st.shape != (B, 3) or acc.dim() != 3:
+                raise ValueError(f"blend: starts (B, 3) and a (Z, Yp, Xp) accumulator expected, got {st.shape}, {tuple(acc.shape)}")
+            if np.any(st[:, 0] + D > acc.shape[0]):  # (the hook checks the rest: it knows the Yp x Xp of a plane, not their number)
+                raise ValueError("blend: a window leaves the accumulator's planes")
+            a.starts = st.ctypes.data_as(C.POINTER(C.c_int))
+            a.acc = self._dev(acc, torch.float32, "acc").value
+            a.Yp, a.Xp, a.scale, a.bmin = int(acc.shape[1]), int(acc.shape[2]), float(scale), float(bmin)
+            if bw is not None:
+                if bw.numel() != D + H + W:
+                    raise ValueError("blend: bw holds D + H + W factors")
+                a.bw = self._dev(bw, torch.float32, "bw").value
+            if wsum is not None:
+                if wsum.shape != acc.shape:
+                    raise ValueError("blend: wsum is shaped like acc")
+                a.wsum = self._dev(wsum, torch.float32, "wsum").value
+            out = None
+        else:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            a.out = self._dev(out, torch.float32, "out").value
         a.B, a.D, a.H, a.W = int(B), int(D), int(H), int(W)
         self._check(self.lib.dlv_debug_set_format(self.ctx, PREC_F16 if precision in ("fp16", "f16") else PREC_BF16_ALL))
         self._enter()
@@ -471,6 +496,8 @@ class HipEngine:
                                          "seam": bool(nm & 32)},
             "norm_passes": a.ran_norm_passes,
         }
+        if blend:
+            return report
         if op == "norm" and pool:
             return out, out2, report
         return out, report

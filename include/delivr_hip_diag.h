@@ -78,7 +78,14 @@ int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev
  *                         mode - format fp16: the pooled tensor is written in bf16 (out2 required); format bf16: the activated
  *                         tensor is written in fp16 (no out2).  kind is ignored.
  *   op 4 (DLV_DBG_FINAL)  the final 1x1x1 conv on the raw in1 (B, 32, D, H, W) with scale/shift ss1 -> fp32 logits (B, D, H, W)
- *                         (no blending).  kind is ignored.
+ *                         (no blending).  kind is ignored.  With acc (device fp32, planes of Yp x Xp): the BLEND instantiation
+ *                         through the launcher a pass uses - window n of the forward of a window flipped along flip_dim is
+ *                         un-flipped and added at starts[3n .. 3n+2] = (z, y, x) (host ints, copied by the hook):
+ *                         acc += scale * logit (scale 0: 1), or with bw (device, D + H + W factors)
+ *                         acc += g * logit, wsum (may be NULL) += g, g = max(bw[z] bw[D + y] bw[D + H + x], bmin) * scale at the
+ *                         window coordinate (z, y, x) in volume orientation.  out is not written.  DLV_EINVAL for another
+ *                         flip_dim, a non-finite scale or bmin, wsum without bw, or a window that leaves the Yp x Xp planes (the
+ *                         caller answers for the planes: acc and wsum hold at least max(z) + D of them).
  * kind 0: final output (B, Cout, D, H, W); 2: raw output in the stored scale (see below); 3: scale/shift pairs (float2 [B][Cout]).
  * Reported: ran_zreg (DLV_DBG_ZR_* bits of the z-reg instantiation that ran, 0: another kernel), ran_upconv (1 one tile per
  * workgroup, 2 persistent, 0 none), ran_stem (1: stem_mfma_kernel), and how the raw output relates to conv3d + bias:
@@ -130,6 +137,14 @@ typedef struct dlv_debug_layer_args {
     int ran_conv, ran_tx, ran_ncb, ran_wlds, ran_grid, ran_items;
     int ran_deconv, ran_gpw, ran_pad;
     int ran_norm, ran_norm_passes;
+    /* DLV_DBG_FINAL blending into an accumulator (acc NULL: plain logits, as before) */
+    const int* starts;
+    float* acc;
+    int Yp, Xp;
+    float scale;
+    const float* bw;
+    float bmin;
+    float* wsum;
 } dlv_debug_layer_args;
 int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args);
 

@@ -10,8 +10,8 @@ launch sites); where the row's shape is a level of a window the planner accepts 
 Every row runs B = 3 windows with their own data (B = 9 where the row says so) in both formats and prints a RESULT line.
 tests/test_layer_ref_cpu.py holds the row tables against the launcher lists of the C++ sources.
 
-Left out: the non-temporal instantiations of the norm passes (they need tensors above 768 MiB) and the blend mode of the final
-conv (its index arithmetic is covered by the sliding-window tests with flips and both blends)."""
+Left out: the non-temporal instantiations of the norm passes (they need tensors above 768 MiB).  The blend mode of the final conv
+runs alone, per voxel against float64, in tests/test_gpu_blend_exact.py."""
 from collections import namedtuple
 
 import numpy as np

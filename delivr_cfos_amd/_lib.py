@@ -135,6 +135,12 @@ class CclRan(C.Structure):
                 ("init_per", C.c_uint64), ("blocks", C.c_uint64), ("groups", C.c_uint64), ("list_n", C.c_uint64)]
 
 
+class FinalizeRan(C.Structure):
+    """dlv_finalize_ran (include/delivr_hip_diag.h): what the last finalize of a context launched."""
+    _fields_ = [(name, C.c_int) for name in ("xy_form", "nc", "y_v", "z_form", "z_v", "nblk", "zphase", "raw_vec", "dist_vec",
+                                             "acc_vec")]
+
+
 class SwParams(C.Structure):
     _fields_ = [
         ("Zp", C.c_int), ("Yp", C.c_int), ("Xp", C.c_int),
@@ -246,6 +252,7 @@ SIGNATURES = {
                                             C.c_longlong, C.c_int]),
     "dlv_diag_set": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "dlv_diag_ccl_ran": (C.c_int, [_P, C.POINTER(CclRan)]),
+    "dlv_diag_finalize_ran": (C.c_int, [_P, C.POINTER(FinalizeRan)]),
     "dlv_diag_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.POINTER(LayerPlan)]),
     "dlv_cells_csv": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),

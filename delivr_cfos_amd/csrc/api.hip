@@ -677,6 +677,13 @@ int dlv_diag_ccl_ran(dlv_ctx* ctx, dlv_ccl_ran* out) {
     return DLV_OK;
 }
 
+// what the last finalize of this context launched (finalize.hip records it at the launch sites)
+int dlv_diag_finalize_ran(dlv_ctx* ctx, dlv_finalize_ran* out) {
+    if (!ctx || !out) return DLV_EINVAL;
+    *out = ctx->finalize_ran;
+    return DLV_OK;
+}
+
 int dlv_debug_set_zm_variant(dlv_ctx* ctx, int variant) {
     if (!ctx) return DLV_EINVAL;
 #ifndef DLV_DIAG

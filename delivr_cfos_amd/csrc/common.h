@@ -136,6 +136,7 @@ struct dlv_ctx {
     bool resample_simple = false, resample_run16 = false;
     int ccl_init_grid = 0;   // dlv_diag_set "ccl_init_grid": at most so many workgroups for ccl_init_kernel (0: its own choice; tests)
     dlv_ccl_ran ccl_ran = {};  // what the last dlv_ccl26_dev launched (dlv_diag_ccl_ran)
+    dlv_finalize_ran finalize_ran = {};  // what the last dlv_finalize_dev / dlv_finalize_slab_dev launched (dlv_diag_finalize_ran)
     int tiff_chunk = 0;      // planes per staging chunk of dlv_tiff_stack_to_device (0: ~256 MB; tests: the double-buffer hand-over on small planes)
     bool prof_on = false;
     std::vector<DlvProfSlot> prof_slots;

@@ -461,7 +461,10 @@ extern "C" int dlv_finalize_slab_dev(dlv_ctx* ctx, const float* acc_dev, const u
 
 static int finalize_impl(dlv_ctx* ctx, const float* acc_dev, const uint8_t* cnt_dev, const uint16_t* raw_dev, int Yp, int Xp, int Z,
                          int Y, int X, float threshold, int erode_iters, int zblock, int zphase, uint8_t* out_dev, float* prob_dev) {
-    if (!ctx || !acc_dev || !raw_dev || !out_dev) return DLV_EINVAL;
+    if (!ctx) return DLV_EINVAL;
+    dlv_finalize_ran& ran = ctx->finalize_ran;  // what this call launches (dlv_diag_finalize_ran): written at the launch sites
+    ran = dlv_finalize_ran();
+    if (!acc_dev || !raw_dev || !out_dev) return DLV_EINVAL;
     if (Z <= 0 || Y <= 0 || X <= 0 || Y > Yp || X > Xp) return dlv_fail(ctx, DLV_EINVAL, "bad shapes");
     if (erode_iters < 0 || erode_iters > 253) return dlv_fail(ctx, DLV_EUNSUP, "erode_iters must be in [0,253]");
     if (2 * (size_t)X > 160 * 1024) return dlv_fail(ctx, DLV_EUNSUP, "X=%d exceeds the LDS row buffer", X);
@@ -474,38 +477,52 @@ static int finalize_impl(dlv_ctx* ctx, const float* acc_dev, const uint8_t* cnt_
     const bool v4 = (X % 4 == 0);
     const bool split_xy = ctx->erode_xy_split;  // A/B + cross-check in tests (dlv_diag_set): separate x and y passes
     const int nchunk8 = (X + 7) / 8;
+    // the alignment conditions of erode_xy_kernel / erode_x_bits_kernel, for the record only (the kernels evaluate their own)
+    const int raw_vec = (Xp % 8 == 0) && ((reinterpret_cast<uintptr_t>(raw_dev) & 15) == 0);
+    const int dist_vec = (X % 8 == 0) && ((reinterpret_cast<uintptr_t>(dist) & 7) == 0);
     if (cap <= 57 && nchunk8 <= 1024 && !split_xy) {
         // x and y fused: the x distance never reaches HBM
         DlvProf p(ctx, "erode_xy_u8", 0.0, 5.0 * nvox);
         const size_t lds = 2 * (size_t)(((nchunk8 + 24 + 7) / 8) * 8);
-        if (nchunk8 <= 256)
+        ran.xy_form = 0, ran.raw_vec = raw_vec, ran.dist_vec = dist_vec;
+        if (nchunk8 <= 256) {
             hipLaunchKernelGGL(erode_xy_kernel<1>, dim3((unsigned)Z), dim3(256), lds, ctx->stream, raw_dev, Yp, Xp, Y, X, cap, dist);
-        else if (nchunk8 <= 512)
+            ran.nc = 1;
+        } else if (nchunk8 <= 512) {
             hipLaunchKernelGGL(erode_xy_kernel<2>, dim3((unsigned)Z), dim3(256), lds, ctx->stream, raw_dev, Yp, Xp, Y, X, cap, dist);
-        else
+            ran.nc = 2;
+        } else {
             hipLaunchKernelGGL(erode_xy_kernel<4>, dim3((unsigned)Z), dim3(256), lds, ctx->stream, raw_dev, Yp, Xp, Y, X, cap, dist);
+            ran.nc = 4;
+        }
         p.end();
         DLV_LAUNCH_CHECK(ctx, "erode_xy_kernel");
     } else {
     {
         DlvProf p(ctx, "erode_x_u8", 0.0, 3.0 * nvox);
-        if (cap <= 57)
+        if (cap <= 57) {
             hipLaunchKernelGGL(erode_x_bits_kernel, dim3((unsigned)((long long)Z * Y)), dim3(256), (size_t)((X + 7) / 8 + 24 + 8),
                                ctx->stream, raw_dev, Yp, Xp, Y, X, cap, dist);
-        else
+            ran.xy_form = 1, ran.raw_vec = raw_vec, ran.dist_vec = dist_vec;
+        } else {
             hipLaunchKernelGGL(erode_x_kernel, dim3((unsigned)((long long)Z * Y)), dim3(256), 2 * (size_t)X, ctx->stream,
                                raw_dev, Yp, Xp, Y, X, cap, dist);
+            ran.xy_form = 2;
+        }
         p.end();
         DLV_LAUNCH_CHECK(ctx, "erode_x_kernel");
     }
     {
         DlvProf p(ctx, "erode_y_u8", 0.0, 4.0 * nvox);
-        if (v4)
+        if (v4) {
             hipLaunchKernelGGL(erode_y_kernel<4>, dim3(dlv_cdiv((long long)Z * (X / 4), 256)), dim3(256), 0, ctx->stream,
                                dist, Z, Y, X);
-        else
+            ran.y_v = 4;
+        } else {
             hipLaunchKernelGGL(erode_y_kernel<1>, dim3(dlv_cdiv((long long)Z * X, 256)), dim3(256), 0, ctx->stream, dist,
                                Z, Y, X);
+            ran.y_v = 1;
+        }
         p.end();
         DLV_LAUNCH_CHECK(ctx, "erode_y_kernel");
     }
@@ -514,23 +531,30 @@ static int finalize_impl(dlv_ctx* ctx, const float* acc_dev, const uint8_t* cnt_
         const int nblk = (int)(((long long)Z + zphase + zblock - 1) / zblock);
         DlvProf p(ctx, "erode_z_final", 0.0, (4.0 + 4.0 + 1.0) * nvox);
         const bool two_sweeps = ctx->erode_z_two_sweeps;  // A/B + cross-check in tests (dlv_diag_set)
+        ran.nblk = nblk, ran.zphase = zphase;
         if (erode_iters <= 31 && !two_sweeps) {  // one sweep with a shift register per column (the reference's 30 iterations)
-            if (v4)
+            ran.z_form = 0;
+            if (v4) {
                 hipLaunchKernelGGL(erode_z_shift_kernel<4>, dim3(dlv_cdiv((long long)nblk * Y * (X / 4), 256)), dim3(256), 0,
                                    ctx->stream, dist, acc_dev, cnt_dev, Yp, Xp, Z, Y, X, zblock, zphase, erode_iters, threshold,
                                    out_dev, prob_dev);
-            else
+                ran.z_v = 4, ran.acc_vec = (Xp % 4 == 0) && ((reinterpret_cast<uintptr_t>(acc_dev) & 15) == 0);
+            } else {
                 hipLaunchKernelGGL(erode_z_shift_kernel<1>, dim3(dlv_cdiv((long long)nblk * Y * X, 256)), dim3(256), 0,
                                    ctx->stream, dist, acc_dev, cnt_dev, Yp, Xp, Z, Y, X, zblock, zphase, erode_iters, threshold,
                                    out_dev, prob_dev);
+                ran.z_v = 1;
+            }
         } else if (v4) {
             hipLaunchKernelGGL(erode_z_final_kernel<4>, dim3(dlv_cdiv((long long)nblk * Y * (X / 4), 256)), dim3(256), 0,
                                ctx->stream, dist, acc_dev, cnt_dev, Yp, Xp, Z, Y, X, zblock, zphase, erode_iters, threshold,
                                out_dev, prob_dev);
+            ran.z_form = 1, ran.z_v = 4;
         } else {
             hipLaunchKernelGGL(erode_z_final_kernel<1>, dim3(dlv_cdiv((long long)nblk * Y * X, 256)), dim3(256), 0,
                                ctx->stream, dist, acc_dev, cnt_dev, Yp, Xp, Z, Y, X, zblock, zphase, erode_iters, threshold,
                                out_dev, prob_dev);
+            ran.z_form = 1, ran.z_v = 1;
         }
         p.end();
         DLV_LAUNCH_CHECK(ctx, "erode_z_final_kernel");

@@ -621,6 +621,12 @@ class HipEngine:
         self._leave()
         return (out, prob) if want_prob else out
 
+    def finalize_ran(self) -> dict:
+        """what the last finalize / finalize_slab of this context launched (include/delivr_hip_diag.h: dlv_finalize_ran) - tests"""
+        out = _lib.FinalizeRan()
+        self._check(self.lib.dlv_diag_finalize_ran(self.ctx, C.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in out._fields_}
+
     # ---- connected components ----------------------------------------------------------------------
     def ccl26(self, mask):
         """uint8 (Z,Y,X) in HBM -> (labels uint32 tensor in HBM (stored in an int32 tensor), N)."""

@@ -236,6 +236,8 @@ int dlv_sw_infer_sharded_wsum(dlv_comm* c, const dlv_sw_params* p, const dlv_sha
  * a caller with another threshold must pass the count map (the Python mirror enforces it).  fg = sigmoid(mean) >= threshold, keep = raw>0 eroded
  * by an L1 ball of radius erode_iters evaluated inside z-blocks of zblock planes (0 = whole
  * volume; the reference's Arrayterator rule gives floor(floor(1e9/X)/Y)), out = fg & keep.
+ * erode_iters in [0, 253]; 0 means NO erosion (keep = raw > 0), unlike scipy's binary_erosion(iterations=0), which repeats
+ * until nothing changes.
  * acc/cnt/raw are (.,Yp,Xp)-strided padded buffers, out_dev is the unpadded (Z,Y,X) uint8
  * binaries.npy payload; prob_dev (nullable) receives sigmoid(mean) as fp32 (Z,Y,X)
  * (network_output.npy, inference.py:312-318). */

@@ -44,6 +44,26 @@ typedef struct dlv_ccl_ran {
 } dlv_ccl_ran;
 int dlv_diag_ccl_ran(dlv_ctx* ctx, dlv_ccl_ran* out);
 
+/* What the last dlv_finalize_dev / dlv_finalize_slab_dev of this context launched, recorded at its launch sites (reset at the
+ * start of every call; all 0 after a call that was refused before its first launch, and before the first call):
+ *   xy_form   0: erode_xy_kernel (x and y fused), 1: erode_x_bits_kernel + erode_y_kernel, 2: erode_x_kernel (log-step) +
+ *             erode_y_kernel
+ *   nc        8-voxel chunks per thread of erode_xy_kernel (1 / 2 / 4; 0 when not fused)
+ *   y_v       voxels per thread of erode_y_kernel (4 / 1; 0 when fused)
+ *   z_form    0: erode_z_shift_kernel (one sweep), 1: erode_z_final_kernel (two sweeps); z_v: its voxels per thread (4 / 1)
+ *   nblk      z-blocks the z kernel walks, zphase: absolute plane of the first local plane modulo the block size
+ *   raw_vec   the kernel that reads the raw volume takes whole 8-voxel chunks with 16-byte loads (Xp % 8 == 0 and the volume on a
+ *             16-byte boundary: every row then starts on one; always 0 for the log-step kernel)
+ *   dist_vec  ... and stores their distances with 8-byte stores (X % 8 == 0 and the distance map on an 8-byte boundary; always
+ *             0 for the log-step kernel)
+ *   acc_vec   erode_z_shift_kernel<4> reads the sums with 16-byte loads (Xp % 4 == 0 and the sums on a 16-byte boundary; 0 for
+ *             every other z kernel)
+ * The three *_vec fields are the host-side values of the conditions the kernels evaluate. */
+typedef struct dlv_finalize_ran {
+    int xy_form, nc, y_v, z_form, z_v, nblk, zphase, raw_vec, dist_vec, acc_vec;
+} dlv_finalize_ran;
+int dlv_diag_finalize_ran(dlv_ctx* ctx, dlv_finalize_ran* out);
+
 /* Diagnostic library only (libdelivr_hip_diag.so, `make diag`): selects an A/B, stamped or timing-only build of the
  * LDS-weights z-marching conv (3/4/6 tile, stagger and streaming-store variants; 20/24 double-buffered half-planes; 40
  * software-pipelined step; 11-13, 30, 41-45 timing-only or stamped builds, profiles/README.md).  The PRODUCT library holds

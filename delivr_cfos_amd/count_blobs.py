@@ -4,6 +4,7 @@ components + statistics on the device instead of cc3d, same files out.
 in : <path_in>/<brain>/binary_segmentations/binaries.npy ('|u1', (Z,Y,X), 128-byte header)   (:45-46)
 out: <post_out>/<brain>-<N>-cc3d.npy (labels), <post_out>/<brain>-stats.pickle
      (dict voxel_counts / bounding_boxes / centroids), <post_out>(Z, Y, X)_<brain>.csv          (:65,86-88,113-114)
+     with settings["mi355x"]["label_file"] = "runs": <post_out>/<brain>-<N>-cc3d.runs (label_runs.py) in place of the .npy labels
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from . import hostio
+from . import hostio, label_runs
 from .hostlogic import (QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_intensity_csv_text,
                         cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget, count_options, csv_name,
                         finish_intensity, finish_quartiles, finish_shape, finish_shell, finish_shell_quartiles, finish_split,
@@ -36,6 +37,20 @@ def load_cached_brain(settings, brain):
 def load_cached_stats(settings, brain):
     """reference :23-34"""
     return _find_cached(settings["postprocessing"]["output_location"], ".pickle", brain)
+
+
+def load_cached_runs(settings, brain):
+    """The cached labelling of a run with settings["mi355x"]["label_file"] = "runs": the LAST directory entry (as _find_cached)
+    named <brain>-<N>-cc3d.runs in the output folder -> (path, N from the name), or False.  The name holds no ".npy": the dense
+    look-up above never matches it."""
+    path = settings["postprocessing"]["output_location"]
+    hits = [x for x in os.listdir(path) if x.startswith(brain + "-") and x.endswith(label_runs.SUFFIX)]
+    if not hits:
+        return False
+    n = hits[-1][len(brain) + 1:-len(label_runs.SUFFIX)]
+    if not n.isdigit():
+        raise ValueError(f"count_blobs: {os.path.join(path, hits[-1])}: no component count between the brain's name and {label_runs.SUFFIX}")
+    return os.path.join(path, hits[-1]), int(n)
 
 
 def _label_dtype(n: int):
@@ -408,7 +423,17 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     "n_after", "components_split"}.  A cached label file is reused as it is: it is NOT split again.  Needs 8 more bytes of HBM per
     voxel while it runs; a mask that needs the slab-streamed path is refused.  Under torch.distributed the key is refused with
     ValueError on every rank: the growth has no bounded reach, so a slab cannot be split on its own.  Off, 0 or absent: nothing of
-    this happens."""
+    this happens.
+
+    ``settings["mi355x"]["label_file"]`` = "runs": the final labels - after the split and the size filter - are run-length coded on
+    the device (HipEngine.cc_runs_encode) and written as <brain>-<N>-cc3d.runs (label_runs.py: the format, and load_labels for the
+    steps that read it) by the same side thread, under the same ``defer_write`` contract; NO dense .npy file is written and the label
+    volume never crosses PCIe.  Statistics, CSV and tables are what they are without the key, and ``count_blobs.last_timings`` gains
+    runs_encode_s.  A dense .npy cache still wins; without one a run file in the output folder is the cached labelling (N from its
+    name, checked against its header; the file is validated in full), not split or filtered again, and decoded into HBM only when
+    something is still to be measured - with a complete pickle nothing is uploaded.  Decoded labels above the HBM budget and a mask
+    that needs the slab-streamed path are refused (MemoryError), torch.distributed is refused with ValueError on every rank.
+    "dense" or absent: nothing of this happens, and a .runs file in the folder is ignored."""
     from .engine import shared_engine
 
     count_blobs.last_filter = None  # set by a run that filtered
@@ -435,6 +460,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['split_fused'] = {split[0]} is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
                          "its own; run step 3 on one device or switch split_fused off")
+    if sharded and opts.runs_file:
+        # (as for split_fused: all raise, before any collective, or none does)
+        raise ValueError(f"count_blobs: settings['mi355x']['label_file'] = \"runs\" is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): every rank writes its slab into the one dense label file, and the runs of a "
+                         "slab are not a part of the volume's run file; run step 3 on one device or leave label_file at \"dense\"")
     if sharded and opts.quartiles:
         # (as for split_fused: all raise, before any collective, or none does)
         raise ValueError(f"count_blobs: settings['mi355x']['intensity_quartiles'] is not available under torch.distributed "
@@ -555,14 +585,18 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
         t_prev[0] = now
     try:
         cached = load_cached_brain(settings, brain)
+        # (a dense cache wins, as without the key; without one, and with label_file = "runs", a run file is the cached labelling)
+        cached_runs = load_cached_runs(settings, brain) if opts.runs_file and not cached else False
+        runs = None
         from .streaming import ccl_bytes_per_voxel, ccl_streamed, hbm_budget_bytes
 
         budget = hbm_budget_bytes(eng, settings)
         need = int(bin_img.size) * ccl_bytes_per_voxel()
         Z = int(bin_img.shape[0])
-        if not cached:  # (size_filter is judged here too: refused exactly when the mask would be slab-streamed)
+        fresh = not cached and not cached_runs
+        if fresh:  # (size_filter is judged here too: refused exactly when the mask would be slab-streamed)
             check_hbm_budget(opts, measuring_plan(opts, None), False, ccl_bytes_per_voxel(), int(bin_img.size), budget)
-        if not cached and need > budget:
+        if fresh and need > budget:
             # the mask + its uint32 labels do not fit this GPU: Z-slabs through the device, seams merged on the host
             # (streaming.py) - the reference's counterpart is cc3d writing into an out_file memmap (:59-64)
             plane = int(bin_img.shape[1]) * int(bin_img.shape[2]) * ccl_bytes_per_voxel()
@@ -587,7 +621,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             with open(os.path.join(path_out, f"{brain}-stats.pickle"), "wb") as fh:
                 pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
             return N, stats, wait
-        if not cached:
+        if fresh:
             print("No cached brain found, performing connected components on the GPU...")
             # binaries.npy -> HBM and the label volume -> its .npy both stream through pinned staging with parallel
             # readers / writers (hostio.py): 4.3 GB in and 17 GB out for a 1024 x 2048 x 2048 brain, around 20 ms of kernels
@@ -612,15 +646,23 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                     split_parent = np.concatenate([split_parent[:1], split_parent[1:][_keep_mask(counts, bounds)[1:]]])
                 del counts_dev
                 mark("size_filter")
-            final = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
-            # (written as <name>.partial and renamed: never a partly written file under the cache's name) - by a side thread that
-            # touches torch's copy stream only, never the context, while this thread goes on to the statistics and the CSV
-            file_labels = _labels_in_file_dtype(labels_dev, N)
-            eng.sync()
             from concurrent.futures import ThreadPoolExecutor
 
             writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dlv-labels")
-            fut = writer.submit(hostio.save_npy, eng, file_labels, final, _label_dtype(N), "d2h_labels", True, True)
+            if opts.runs_file:
+                # the labels are coded in HBM: megabytes of runs cross PCIe and reach <brain>-<N>-cc3d.runs, no dense file is written
+                # (as below: <name>.partial and a rename, on a side thread - which touches host arrays only)
+                fresh_runs = eng.cc_runs_encode(labels_dev)
+                mark("runs_encode")
+                fut = writer.submit(label_runs.save_runs, os.path.join(path_out, label_runs.runs_name(brain, N)), fresh_runs, N)
+                del fresh_runs
+            else:
+                final = os.path.join(path_out, f"{brain}-{N}-cc3d.npy")
+                # (written as <name>.partial and renamed: never a partly written file under the cache's name) - by a side thread that
+                # touches torch's copy stream only, never the context, while this thread goes on to the statistics and the CSV
+                file_labels = _labels_in_file_dtype(labels_dev, N)
+                eng.sync()
+                fut = writer.submit(hostio.save_npy, eng, file_labels, final, _label_dtype(N), "d2h_labels", True, True)
 
             def wait(fut=fut, writer=writer):
                 try:
@@ -631,14 +673,21 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             labels = None
             mark("start_label_write")
         else:
-            N = int(cached.split("/")[-1].split("-")[1])
+            if cached_runs:
+                cached, N = cached_runs
+                runs = label_runs.load_runs(cached)  # (validated in full before anything is decoded or uploaded)
+                if runs["n"] != N or tuple(runs["shape"]) != tuple(int(v) for v in bin_img.shape):
+                    raise ValueError(f"count_blobs: {cached} holds {runs['n']} components of a volume of shape {tuple(runs['shape'])}, its "
+                                     f"name and the mask say {N} components and {tuple(int(v) for v in bin_img.shape)}")
+            else:
+                N = int(cached.split("/")[-1].split("-")[1])
             print(f"Cached brain found at {cached} with {N} components, loading...")
             if opts.filter_active:
                 print(f"size filter: the cached labelling is reused as it is, min_size {bounds[0]} / max_size {bounds[1]} are not applied to it")
             if split is not None:
                 print(f"split of fused cells: the cached labelling is reused as it is, it is not split (depth {split[0]}) again")
             split_parent = None
-            labels = np.load(cached, mmap_mode="r")
+            labels = None if runs is not None else np.load(cached, mmap_mode="r")
         mid = datetime.datetime.now()
         print(f"{mid} labelling+writing/loading took {mid - start} : {N}")
         cached_stats = load_cached_stats(settings, brain)
@@ -646,6 +695,8 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
         def cached_labels_to_device():
             import torch
 
+            if runs is not None:  # (decoded in HBM from the runs: only they cross PCIe)
+                return eng.cc_runs_decode(runs)
             if labels.dtype == np.uint32:
                 return hostio.upload(eng, labels, what="h2d_labels")
             if labels.dtype == np.uint16:  # widened in HBM, not on the host
@@ -663,9 +714,11 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                 stats = pickle.load(fh)
         plan = measuring_plan(opts, stats)  # (what the cached pickle lacks; without one, all that is asked for)
         if labels_dev is None:
-            check_hbm_budget(opts, plan, True, 4, int(labels.size), budget)
+            # (a run file is decoded only when something is still to be measured; with a complete pickle nothing is uploaded)
+            check_hbm_budget(opts, plan, True, 4, int(bin_img.size if runs is not None else labels.size), budget,
+                             runs_decoded=runs is not None and bool(plan or not cached_stats))
         if not cached_stats:
-            if labels_dev is None and int(labels.size) * 4 > budget:
+            if labels_dev is None and runs is None and int(labels.size) * 4 > budget:
                 # cached labels that do not fit the HBM budget: statistics slab by slab (raw sums add up; streaming.py)
                 from .streaming import stats_streamed
 

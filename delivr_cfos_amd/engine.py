@@ -890,6 +890,63 @@ class HipEngine:
         K = int(k.value)
         return K, parent[:K + 1].cpu().numpy().view(np.uint32), int(n_split.value)
 
+    def cc_runs_encode(self, labels) -> dict:
+        """The run-length coding of a label volume in HBM (dlv_cc_runs_count_dev, dlv_cc_runs_emit_dev; the format and the numpy
+        reference: label_runs.py).  labels: int32 (uint32 payload) (Z,Y,X) in HBM, contiguous, X <= 65536.  -> {"row_start": uint64
+        (Z*Y + 1), "x0", "x1": uint16 (R), "label": uint32 (R), "shape": (Z, Y, X)} on the host - label_runs.encode_runs' dict."""
+        torch = self.torch
+        Z, Y, X = self._label_volume("cc_runs_encode", labels)
+        row_start = torch.empty(Z * Y + 1, dtype=torch.int64, device=self.device)  # uint64 payload
+        n_runs = C.c_uint64()
+        self._enter()
+        try:
+            self._check(self.lib.dlv_cc_runs_count_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, C.c_void_p(row_start.data_ptr()),
+                                                       C.byref(n_runs)))
+            R = int(n_runs.value)
+            x0 = torch.empty(R, dtype=torch.int16, device=self.device)
+            x1 = torch.empty(R, dtype=torch.int16, device=self.device)
+            label = torch.empty(R, dtype=torch.int32, device=self.device)
+            self._check(self.lib.dlv_cc_runs_emit_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, C.c_void_p(row_start.data_ptr()), R,
+                                                      *(C.c_void_p(t.data_ptr()) if R else None for t in (x0, x1, label))))
+        finally:
+            self._leave()
+        return {"row_start": row_start.cpu().numpy().view(np.uint64), "x0": x0.cpu().numpy().view(np.uint16),
+                "x1": x1.cpu().numpy().view(np.uint16), "label": label.cpu().numpy().view(np.uint32), "shape": (Z, Y, X)}
+
+    def cc_runs_decode(self, runs: dict, z0: int = 0, z1: Optional[int] = None, out=None):
+        """The planes [z0, z1) of the label volume a run-length coding holds, decoded into HBM (dlv_cc_runs_decode_dev).  runs: the
+        dict of cc_runs_encode / label_runs.load_runs (validated there: the kernel clamps what it reads, it does not judge it).
+        Only the rows' slice of row_start and their runs are uploaded.  out: an int32 tensor (z1 - z0, Y, X) in HBM to decode into
+        (it need not be cleared).  -> int32 tensor (uint32 payload) (z1 - z0, Y, X), every voxel written."""
+        torch = self.torch
+        Z, Y, X = (int(v) for v in runs["shape"])
+        z0, z1 = int(z0), Z if z1 is None else int(z1)
+        if not 0 <= z0 < z1 <= Z:
+            raise ValueError(f"cc_runs_decode: planes [{z0}, {z1}) do not lie in the {Z} planes of the coding")
+        rs = np.ascontiguousarray(runs["row_start"][z0 * Y:z1 * Y + 1], dtype=np.uint64)
+        a, b = int(rs[0]), int(rs[-1])
+        if len(rs) != (z1 - z0) * Y + 1 or not a <= b <= min(len(runs[k]) for k in ("x0", "x1", "label")):
+            raise ValueError("cc_runs_decode: row_start does not match the shape and the run arrays")
+
+        def dev(arr, np_dtype, as_int):  # (unsigned payloads in torch's signed types)
+            return torch.from_numpy(np.ascontiguousarray(arr, dtype=np_dtype).view(as_int)).to(self.device)
+
+        rs_dev = dev(rs, np.uint64, np.int64)
+        x0, x1 = dev(runs["x0"][a:b], np.uint16, np.int16), dev(runs["x1"][a:b], np.uint16, np.int16)
+        label = dev(runs["label"][a:b], np.uint32, np.int32)
+        if out is None:
+            out = torch.empty((z1 - z0, Y, X), dtype=torch.int32, device=self.device)
+        elif self._label_volume("cc_runs_decode", out) != (z1 - z0, Y, X):
+            raise ValueError(f"cc_runs_decode: out of shape {tuple(out.shape)}, the planes [{z0}, {z1}) are {(z1 - z0, Y, X)}")
+        self._enter()
+        try:
+            self._check(self.lib.dlv_cc_runs_decode_dev(self.ctx, C.c_void_p(rs_dev.data_ptr()), (z1 - z0) * Y, X,
+                                                        *(C.c_void_p(t.data_ptr()) if b > a else None for t in (x0, x1, label)), b - a,
+                                                        C.c_void_p(out.data_ptr())))
+        finally:
+            self._leave()  # (torch's stream now waits for the kernel: the uploaded runs freed here are not reused before it)
+        return out
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

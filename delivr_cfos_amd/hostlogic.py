@@ -481,6 +481,21 @@ def cell_shape_csv_text(stats: dict, n: int) -> str:
     return "\n".join(lines) + "\n"
 
 
+LABEL_FILE_FORMATS = ("dense", "runs")
+
+
+def label_file_format(settings) -> str:
+    """settings["mi355x"]["label_file"]: "dense" (or absent) - the reference's <brain>-<N>-cc3d.npy; "runs" - the run-length file
+    <brain>-<N>-cc3d.runs (label_runs.py) in its place.  ValueError for anything else."""
+    value = ((settings or {}).get("mi355x") or {}).get("label_file")
+    if value is None:
+        return "dense"
+    if not isinstance(value, str) or value not in LABEL_FILE_FORMATS:
+        raise ValueError(f"settings['mi355x']['label_file'] = {value!r}: expected \"dense\" (the default: the reference's .npy label "
+                         "volume) or \"runs\" (the run-length label file)")
+    return value
+
+
 @dataclass(frozen=True)
 class CountOptions:
     """count_blobs' opt-in keys of settings["mi355x"], each as its parser returns it (count_options builds the record from the
@@ -491,6 +506,12 @@ class CountOptions:
     quartiles: bool = False  # intensity_quartiles_enabled
     shape: bool = False  # shape_stats_enabled
     split: Optional[Tuple[int, int]] = None  # split_fused_settings
+    label_file: str = "dense"  # label_file_format
+
+    @property
+    def runs_file(self) -> bool:
+        """the labels go to (and a cached labelling may come from) the run-length file"""
+        return self.label_file == "runs"
 
     @property
     def filter_active(self) -> bool:
@@ -512,7 +533,7 @@ def count_options(settings, min_size, max_size) -> CountOptions:
     split = split_fused_settings(settings)
     shape = shape_stats_enabled(settings)
     return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
-                        shape=shape, split=split)
+                        shape=shape, split=split, label_file=label_file_format(settings))
 
 
 INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
@@ -539,16 +560,17 @@ def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
 
 
-_HBM_FRESH = ("intensity_stats", "background_shell", "intensity_quartiles", "shape_stats", "split_fused", "size_filter")
-_HBM_CACHED = ("shape_stats", "intensity_stats", "background_shell", "intensity_quartiles")  # (cached labels are not split or filtered)
+_HBM_FRESH = ("intensity_stats", "background_shell", "intensity_quartiles", "shape_stats", "split_fused", "size_filter", "label_file")
+_HBM_CACHED = ("label_file", "shape_stats", "intensity_stats", "background_shell", "intensity_quartiles")  # (cached labels are not split or filtered)
 
 
-def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxels: int, budget: int) -> None:
+def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxels: int, budget: int, runs_decoded: bool = False) -> None:
     """count_blobs' HBM check of the opt-in keys.  Resident are `base` bytes per voxel: the mask and its labels of a fresh labelling
     (streaming.ccl_bytes_per_voxel()), or the cached labels (4).  measured: the groups (measuring_plan) that are going to be taken -
     of a fresh labelling all that are asked for, measuring_plan(opts, None).  MemoryError for the first key, in the order the work
     is done, whose volumes do not fit `budget` bytes beside that; a fresh labelling above the budget alone is slab-streamed
-    (streaming.py), which measures, splits and filters nothing."""
+    (streaming.py), which measures, splits and filters nothing and writes the dense label file only.  runs_decoded: the cached
+    labelling is a run-length file that is about to be decoded into HBM (there is no slab-wise way round that)."""
     resident = "the cached labels" if cached else "the mask and its labels"
     raw = bool(RAW_GROUPS & measured)
     s = opts.shell_bytes_per_voxel
@@ -562,6 +584,7 @@ def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxe
         "split_fused": (opts.split is not None, f" = {opts.split and opts.split[0]}", 8,
                         f"8 more bytes per voxel in HBM beside {resident}", "split"),
         "size_filter": (opts.filter_active, "", 0, f"{resident} in HBM", "filter"),
+        "label_file": (opts.runs_file and (runs_decoded or not cached), ' = "runs"', 0, f"{resident} in HBM", "write run-length labels"),
     }
     for key in _HBM_CACHED if cached else _HBM_FRESH:
         applies, value, extra, clause, lacks = rows[key]

@@ -366,6 +366,26 @@ int dlv_cc_shape_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Zb, int Y, in
 int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int depth, int64_t min_core,
                      uint32_t* work_a_dev, uint32_t* work_b_dev, uint64_t* n_out, uint64_t* n_split_out,
                      uint32_t* parent_dev, uint64_t parent_cap);
+/* The run-length coding of a label volume and its decoder (no counterpart in the reference, which writes the dense volume; the
+ * format: delivr_cfos_amd/label_runs.py). labels_dev: uint32 (Z,Y,X) contiguous, 4-byte aligned, labels below 2^32 - 1. A run is a
+ * maximal stretch of one non-zero label inside a row (z, y): it never crosses a row's end, and two touching runs of different labels
+ * are two runs. Runs are in raster order, so a volume has one coding.
+ *  dlv_cc_runs_count_dev: row_start_dev[r] = the runs of the rows before row r = z*Y + y (uint64, Z*Y + 1 entries on the device, the
+ *    last one the number of runs R), *n_runs = R on the host. Synchronous.
+ *  dlv_cc_runs_emit_dev: with row_start_dev and n_runs of the count on the same labels, run k's first x, last x (inclusive, so
+ *    X = 65536 fits) and label go to x0_dev[k], x1_dev[k], label_dev[k] (n_runs entries each; may be NULL with n_runs == 0).
+ *    Nothing is written at or beyond n_runs. Asynchronous on the context's stream.
+ *  dlv_cc_runs_decode_dev: rows [0, n_rows) of a uint32 volume of row length X from row_start_dev (n_rows + 1 entries, rebased by
+ *    its first one: a range of planes is a slice of the table) and the n_runs runs those rows hold. EVERY voxel of the rows is
+ *    written, zeros included; a run is clamped to its row and a run index to n_runs, whatever the arrays hold. Asynchronous on the
+ *    context's stream.
+ * Integer work only: exact and independent of scheduling. A NULL pointer, Z/Y/X (n_rows) < 1 or a pointer not aligned to its
+ * element: DLV_EINVAL; X above 65536: DLV_EUNSUP (as dlv_cc_shape_dev); nothing is written then. */
+int dlv_cc_runs_count_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t* row_start_dev, uint64_t* n_runs);
+int dlv_cc_runs_emit_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, const uint64_t* row_start_dev, uint64_t n_runs,
+                         uint16_t* x0_dev, uint16_t* x1_dev, uint32_t* label_dev);
+int dlv_cc_runs_decode_dev(dlv_ctx* ctx, const uint64_t* row_start_dev, uint64_t n_rows, int X, const uint16_t* x0_dev,
+                           const uint16_t* x1_dev, const uint32_t* label_dev, uint64_t n_runs, uint32_t* labels_out_dev);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

@@ -260,11 +260,7 @@ SIGNATURES = {
                                 C.c_int, C.c_int, C.POINTER(LayerPlan)]),
     "dlv_cells_csv": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dlv_reserve_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
-    "dlv_debug_stamps": (C.c_int, [_P, _P]),
-    "dlv_debug_set_zm_variant": (C.c_int, [_P, C.c_int]),
     "dlv_debug_set_format": (C.c_int, [_P, C.c_int]),
-    "dlv_debug_layer_bf16": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
-                                       C.c_int]),
     "dlv_debug_layer16": (C.c_int, [_P, C.POINTER(DebugLayerArgs)]),
     "dlv_unet_set_conv_shift": (C.c_int, [_P, C.c_int, C.c_int]),
     "dlv_unet_get_conv_shift": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),

@@ -278,9 +278,6 @@ int dlv_ctx_create(int device_id, void* stream, dlv_ctx** out) {
     dlv_ctx* ctx = new (std::nothrow) dlv_ctx();
     if (!ctx) return DLV_ENOMEM;
     ctx->device = device_id;
-#ifdef DLV_DIAG  // the product library takes no kernel variant from the environment (diagnostic builds: make diag)
-    if (const char* e = getenv("DLV_ZM_VARIANT")) ctx->sw.zm_variant = atoi(e);
-#endif
 #ifdef DLV_DIAG  // timing-only ablations (WRONG results): the diagnostic library only (make diag), never the product
     ctx->upconv_dbg = getenv("DLV_UPCONV_DBG") ? atoi(getenv("DLV_UPCONV_DBG")) : 0;
 #endif
@@ -298,7 +295,6 @@ int dlv_ctx_create(int device_id, void* stream, dlv_ctx** out) {
         ctx->own_stream = true;
     }
     ctx->main_stream = ctx->stream;
-    if (hipMalloc(&ctx->zero_page, 256) == hipSuccess) (void)hipMemset(ctx->zero_page, 0, 256);
     if (hipMalloc((void**)&ctx->range_flag, 256) != hipSuccess || hipMemset(ctx->range_flag, 0, 256) != hipSuccess) {
         (void)dlv_ctx_destroy(ctx);
         return DLV_ENOMEM;
@@ -333,7 +329,6 @@ int dlv_ctx_destroy(dlv_ctx* ctx) {
     for (int i = 0; i < WS_N_SLOTS; ++i)
         if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
     if (ctx->blob) (void)hipFree(ctx->blob);
-    if (ctx->zero_page) (void)hipFree(ctx->zero_page);
     if (ctx->range_flag) (void)hipFree(ctx->range_flag);
     for (int k = 0; k < DLV_MAX_LANES - 1; ++k)
         if (ctx->aux[k]) {
@@ -655,8 +650,12 @@ int dlv_cells_csv(const uint32_t* voxel_counts, const double* centroids, uint64_
 int dlv_diag_set(dlv_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return DLV_EINVAL;
     const std::string n(name);
-    if (n == "zm_variant") return dlv_debug_set_zm_variant(ctx, value);  // (the product library refuses the diagnostic builds)
-    if (dlv_plan_switch_set(ctx->sw, name, value)) return DLV_OK;        // the switches that choose a layer's kernel (layer_plan.h)
+    switch (dlv_plan_switch_set(ctx->sw, name, value)) {  // the switches that choose a layer's kernel (layer_plan.h)
+        case DLV_SWITCH_SET: return DLV_OK;
+        case DLV_SWITCH_REFUSED:
+            return dlv_fail(ctx, DLV_EUNSUP, "dlv_diag_set: %s = %d selects a build that was retired (0, 50 and 51 are left)", name, value);
+        case DLV_SWITCH_UNKNOWN: break;
+    }
     if (n == "upconv_simple") ctx->upconv_simple = value ? 1 : 0;
     else if (n == "zreg_dbg") ctx->zreg_dbg = value;
     else if (n == "erode_xy_split") ctx->erode_xy_split = value != 0;
@@ -684,18 +683,6 @@ int dlv_diag_finalize_ran(dlv_ctx* ctx, dlv_finalize_ran* out) {
     return DLV_OK;
 }
 
-int dlv_debug_set_zm_variant(dlv_ctx* ctx, int variant) {
-    if (!ctx) return DLV_EINVAL;
-#ifndef DLV_DIAG
-    // product library: 0 / 50 = register-resident-weights conv (default), 51 = the LDS-resident-weights kernel for every
-    // z-march layer (A/B); the timing-only, stamped and experimental builds exist in libdelivr_hip_diag.so only
-    if (variant != 0 && variant != 50 && variant != 51)
-        return dlv_fail(ctx, DLV_EUNSUP, "z-march variant %d is a diagnostic build: load libdelivr_hip_diag.so (make -C delivr_cfos_amd/csrc diag)", variant);
-#endif
-    ctx->sw.zm_variant = variant;
-    return DLV_OK;
-}
-
 // the plan of one forward of a sliding-window pass, on the host alone (layer_plan.h)
 int dlv_diag_plan(const int features[6], const char* const* names, const int* values, int n, int fmt16, int B, int d, int h, int w,
                   dlv_layer_plan* out) {
@@ -706,15 +693,9 @@ int dlv_diag_plan(const int features[6], const char* const* names, const int* va
         if (!names[i]) return DLV_EINVAL;
         if (strcmp(names[i], "upconv_simple") == 0) upconv_simple = values[i] != 0;  // (no kernel family: the upconv label's "m")
         else if (strcmp(names[i], "zreg_dbg") == 0) continue;  // (another code path of the same kernel)
-        else if (!dlv_plan_switch_set(sw, names[i], values[i])) return DLV_EINVAL;
+        else if (dlv_plan_switch_set(sw, names[i], values[i]) != DLV_SWITCH_SET) return DLV_EINVAL;
     }
     return dlv_plan_forward(sw, upconv_simple, features, fmt16, B, d, h, w, out) ? DLV_OK : DLV_EUNSUP;
-}
-
-int dlv_debug_stamps(dlv_ctx* ctx, void* buf_dev) {
-    if (!ctx) return DLV_EINVAL;
-    ctx->stamp_buf = buf_dev;
-    return DLV_OK;
 }
 
 int dlv_debug_set_format(dlv_ctx* ctx, int precision) {

@@ -98,7 +98,6 @@ struct dlv_ctx {
     float* blend_wsum = nullptr;
     int upconv_dbg = 0;         // DLV_UPCONV_DBG, diagnostic library only (timing, WRONG results): 1 = no stores, 2 = no halo loads
     int upconv_simple = 0;      // dlv_diag_set "upconv_simple": the one-tile-per-workgroup upconv kernel for every shape (A/B, tests)
-    void* stamp_buf = nullptr;  // dlv_debug_stamps: timeline buffer of the diagnostic z-march build (DLV_ZM_VARIANT=30)
     int* range_flag = nullptr;  // device words: [0] 0, or 100 - (first layer whose InstanceNorm sums were not finite; 18 = logits);
                                 // [1 + layer] float bits of the largest |mean| + 8 sigma of the layer's raw output that exceeded 4096
     int range_last = -1;        // layer of the last DLV_ERANGE (-1: none)
@@ -106,7 +105,6 @@ struct dlv_ctx {
     bool range_seq = false;              // dlv_range_recover has changed shifts since the last pass that came to its end
     int range_base[DLV_N_CONV] = {0};    // ... the shifts before its first step (restored when nothing is left to try)
     int range_blind_layer = -1;          // layer whose last step was blind (no block reported a peak): not repeated
-    void* zero_page = nullptr;  // 256 zero bytes: source of out-of-window lanes of LDS-DMA loads
     void* blob = nullptr;  // one allocation holding every packed parameter
     size_t blob_bytes = 0;
     DlvConvLayer conv[DLV_N_CONV];
@@ -117,7 +115,7 @@ struct dlv_ctx {
     void* ws[WS_N_SLOTS] = {nullptr};
     size_t ws_bytes[WS_N_SLOTS] = {0};
     // timing
-    bool debug_f16 = false;  // format used by dlv_debug_layer_bf16
+    bool debug_f16 = false;  // format used by dlv_debug_layer16
     // Kernel-selection switches of tests and A/B runs that decide which kernel runs a layer (layer_plan.h; dlv_diag_set sets them
     // per context).  The library takes no switch from the environment; what it does read there: DLV_LANES, DLV_LAUNCH_LOG,
     // DLV_RCCL_PATH / ROCM_PATH / DLV_FORCE_RCCL (transport), nothing else.

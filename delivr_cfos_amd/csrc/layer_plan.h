@@ -15,7 +15,7 @@
 // per context.
 struct DlvPlanSwitches {
     bool no_zmarch = false;  // the generic conv kernel, the per-parity transposed conv and the VALU stem everywhere
-    int zm_variant = 0;      // kernel variant of the z-march conv (0 / 50 = default; 51 and the diagnostic builds take the z-reg layers too)
+    int zm_variant = 0;      // 0 / 50 = default; 51 = the LDS-weights z-march conv takes the z-reg layers too (A/B)
     int zreg_mask = 3;       // 1 = Cin 32, 2 = Cin 64 layers may take the register-resident-weights conv
     int deep_mask = 2;       // conv_deep.hip: bit 0 = the layers the LDS-weights z-march also takes, bit 1 = the others
     int deep_small = 1;      // 0 = levels smaller than a tile of conv_deep.hip and its 32-output-channel layers take the generic conv (A/B)
@@ -30,21 +30,26 @@ struct DlvPlanSwitches {
     bool pool_rows_off = false;  // the pooling pass by pooled voxels instead of by full lines
 };
 
-// dlv_diag_set's names of the switches above ("zm_variant": what dlv_debug_set_zm_variant sets); false: not one of them
-inline bool dlv_plan_switch_set(DlvPlanSwitches& s, const char* name, int value) {
+// dlv_diag_set's names of the switches above.  REFUSED: the name is one of them and the value selects nothing - "zm_variant"
+// takes 0, 50 and 51 only (the other numbers selected experiment builds of the z-march conv that were retired; profiles/README.md
+// keeps their measurements).  The context and the host-only planner both come through here, so they refuse the same values.
+enum DlvSwitchResult { DLV_SWITCH_UNKNOWN, DLV_SWITCH_SET, DLV_SWITCH_REFUSED };
+inline DlvSwitchResult dlv_plan_switch_set(DlvPlanSwitches& s, const char* name, int value) {
     const auto is = [&](const char* n) { return strcmp(name, n) == 0; };
     if (is("no_zmarch")) s.no_zmarch = value != 0;
     else if (is("no_upconv")) s.fold_up = value ? 0 : 1;
-    else if (is("zm_variant")) s.zm_variant = value;
-    else if (is("fuse_levels")) s.fuse_levels = value;
+    else if (is("zm_variant")) {
+        if (value != 0 && value != 50 && value != 51) return DLV_SWITCH_REFUSED;
+        s.zm_variant = value;
+    } else if (is("fuse_levels")) s.fuse_levels = value;
     else if (is("fuse_layers")) s.fuse_layers = value;
     else if (is("zreg_mask")) s.zreg_mask = value;
     else if (is("deep_mask")) s.deep_mask = value;
     else if (is("generic_ncb")) s.generic_ncb = value;
     else if (is("deep_small")) s.deep_small = value;
     else if (is("pool_rows_off")) s.pool_rows_off = value != 0;
-    else return false;
-    return true;
+    else return DLV_SWITCH_UNKNOWN;
+    return DLV_SWITCH_SET;
 }
 
 static inline int dlv_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

@@ -846,32 +846,12 @@ int dlv_unet_tiles_bf16(dlv_ctx* ctx, const uint16_t* vol, int Yp, int Xp, const
     return forward_16<PBf16>(ctx, nullptr, vol, Yp, Xp, starts_dev, flip_dim, scale, nullptr, acc, B, d, h, w);
 }
 
-// test hooks (include/delivr_hip_diag.h): one layer of the 16-bit path on fp32 NCDHW tensors (converted on the device) in the
-// format of dlv_debug_set_format.  dlv_debug_layer_bf16 is the older positional form of dlv_debug_layer16.
+// test hook (include/delivr_hip_diag.h): one layer of the 16-bit path on fp32 NCDHW tensors (converted on the device) in the
+// format of dlv_debug_set_format
 extern "C" int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args) {
     if (!ctx || !args || (!args->out && !(args->op == DLV_DBG_FINAL && args->acc))) return DLV_EINVAL;  // (the blend writes no `out`)
     if (!ctx->weights_loaded) return dlv_fail(ctx, DLV_ESTATE, "no weights");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->debug_f16) return debug_layer_16<PF16>(ctx, *args);
     return debug_layer_16<PBf16>(ctx, *args);
-}
-
-extern "C" int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev, int c1, const float* in2_dev,
-                                    int c2, float* out_dev, int B, int D, int H, int W) {
-    if (!in1_dev) return DLV_EINVAL;
-    dlv_debug_layer_args a{};
-    a.kind = kind;
-    a.op = DLV_DBG_CONV;
-    a.index = index;
-    a.in1 = in1_dev;
-    a.c1 = c1;
-    a.in2 = in2_dev;
-    a.c2 = c2;
-    a.flip_dim = -1;
-    a.out = out_dev;
-    a.B = B;
-    a.D = D;
-    a.H = H;
-    a.W = W;
-    return dlv_debug_layer16(ctx, &a);
 }

@@ -361,35 +361,6 @@ class HipEngine:
         reads no such switch from the environment"""
         self._check(self.lib.dlv_diag_set(self.ctx, name.encode(), int(value)))
 
-    def set_zm_variant(self, variant: int) -> None:
-        """A/B and diagnostic builds of the z-march conv (dlv_debug_set_zm_variant); 0 = default."""
-        self._check(self.lib.dlv_debug_set_zm_variant(self.ctx, int(variant)))
-
-    def debug_layer_bf16(self, kind: int, index: int, in1, in2=None, precision: str = "bf16"):
-        """test hook (dlv_debug_layer_bf16): one conv block / deconv of the bf16 path on fp32 tensors."""
-        torch = self.torch
-        B, c1, D, H, W = in1.shape
-        c2 = 0 if in2 is None else int(in2.shape[1])
-        if kind in (0, 2, 3):
-            cout = {i: None for i in range(18)}
-            blk_out = [self.features[0], self.features[0], self.features[1], self.features[1], self.features[2],
-                       self.features[2], self.features[3], self.features[3], self.features[4], self.features[4],
-                       self.features[3], self.features[3], self.features[2], self.features[2], self.features[1],
-                       self.features[1], self.features[5], self.features[5]]
-            out = torch.empty((B, blk_out[index], D, H, W), dtype=torch.float32, device=self.device)
-        else:
-            dco = [self.features[4] // 2, self.features[3] // 2, self.features[2] // 2, self.features[1]]
-            out = torch.empty((B, dco[index], 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=self.device)
-        # (one layer runs in ONE format: "bf16" here is bf16 proper)
-        self._check(self.lib.dlv_debug_set_format(self.ctx, PREC_F16 if precision in ("fp16", "f16") else PREC_BF16_ALL))
-        self._enter()
-        self._check(self.lib.dlv_debug_layer_bf16(
-            self.ctx, kind, index, self._dev(in1, torch.float32, "in1"), int(c1),
-            self._dev(in2, torch.float32, "in2") if in2 is not None else None, c2,
-            self._dev(out, torch.float32, "out"), B, D, H, W))
-        self._leave()
-        return out
-
     _BLOCK_COUT = (0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 3, 3, 2, 2, 1, 1, 5, 5)  # features[] index of each conv block's Cout
 
     def debug_layer16(self, kind: int, op: str = "conv", index: int = 0, in1=None, ss1=None, in2=None, vol=None,

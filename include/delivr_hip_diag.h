@@ -18,6 +18,9 @@ extern "C" {
  *   "zreg_mask" mask      1 = Cin 32, 2 = Cin 64 layers may take the register-resident-weights conv (default 3)
  *   "deep_mask" mask      conv_deep.hip: bit 0 = the layers the LDS-weights z-march also takes, bit 1 = the others (default 2)
  *   "generic_ncb" n       cout blocks per workgroup of the generic conv (0: its own choice)
+ *   "zm_variant" v        0 / 50: default; 51: the LDS-weights z-march conv (conv_zmarch.hip) for every layer the
+ *                         register-resident-weights conv would take (an A/B that gives the same results).  Every other value
+ *                         selected an experiment build of the z-march conv; they were retired and are refused with DLV_EUNSUP.
  *   "zreg_dbg" 1          edge-step code on every plane of the z-reg conv
  *   "deep_small" 0        levels smaller than a tile of conv_deep.hip, and its 32-output-channel layers, take the generic conv
  *   "pool_rows_off" 1     the pooling pass by pooled voxels instead of by full lines
@@ -64,22 +67,10 @@ typedef struct dlv_finalize_ran {
 } dlv_finalize_ran;
 int dlv_diag_finalize_ran(dlv_ctx* ctx, dlv_finalize_ran* out);
 
-/* Diagnostic library only (libdelivr_hip_diag.so, `make diag`): selects an A/B, stamped or timing-only build of the
- * LDS-weights z-marching conv (3/4/6 tile, stagger and streaming-store variants; 20/24 double-buffered half-planes; 40
- * software-pipelined step; 11-13, 30, 41-45 timing-only or stamped builds, profiles/README.md).  The PRODUCT library holds
- * none of them: it accepts 0 / 50 (default: register-resident-weights conv) and 51 (the LDS-weights kernel for every
- * z-march layer, an A/B that gives the same results), refuses every other value with DLV_EUNSUP and ignores the
- * DLV_ZM_VARIANT environment variable.  No reference counterpart. */
-int dlv_debug_set_zm_variant(dlv_ctx* ctx, int variant);
-/* diagnostic: buffer (caller-owned, HBM, >= tiles*8*(D+4)*64 bytes, zeroed) that the stamped build of the z-march
- * conv (DLV_ZM_VARIANT=30) fills with s_memtime stamps of window 0; NULL switches it off.  No reference counterpart. */
-int dlv_debug_stamps(dlv_ctx* ctx, void* buf_dev);
-/* selects the 16-bit format dlv_debug_layer_bf16 runs in (DLV_PREC_BF16 default, DLV_PREC_F16) */
+/* selects the 16-bit format dlv_debug_layer16 runs in (DLV_PREC_BF16 default, DLV_PREC_F16) */
 int dlv_debug_set_format(dlv_ctx* ctx, int precision);
-int dlv_debug_layer_bf16(dlv_ctx* ctx, int kind, int index, const float* in1_dev, int c1, const float* in2_dev,
-                         int c2, float* out_dev, int B, int D, int H, int W);
 
-/* The layer test hook proper (dlv_debug_layer_bf16 forwards to it): one layer of the 16-bit path in the format of
+/* The layer test hook: one layer of the 16-bit path in the format of
  * dlv_debug_set_format, through the same dispatch as a forward, on fp32 NCDHW device tensors.
  *   op 0 (DLV_DBG_CONV)   kind 0/2/3: conv block `index` (1..17) on [in1 (c1), in2 (c2)]; ss1 (device float2 [B][c1], may be
  *                         NULL): in1 is RAW and awaits InstanceNorm scale/shift ss1 + Mish - the dispatcher (fuse_layers /
@@ -170,9 +161,9 @@ int dlv_debug_layer16(dlv_ctx* ctx, dlv_debug_layer_args* args);
 
 /* Which kernel runs each layer of ONE 16-bit forward of a sliding-window pass (stem from the uint16 volume, final conv
  * blending) of B windows of d x h x w, without running it: host arithmetic only (delivr_cfos_amd/csrc/layer_plan.h, what the
- * forward itself consults) - no context, no HIP call, no GPU.  names / values: n switches as given to the switch setter above
- * (plus "zm_variant"); fmt16: 0 = bf16 everywhere, 1 = fp16, 2 = fp16 at level 0 + bf16 below (DLV_PREC_BF16).
- * DLV_EINVAL for an unknown switch, DLV_EUNSUP for features or a window the 16-bit forward refuses. */
+ * forward itself consults) - no context, no HIP call, no GPU.  names / values: n switches as given to the switch setter above;
+ * fmt16: 0 = bf16 everywhere, 1 = fp16, 2 = fp16 at level 0 + bf16 below (DLV_PREC_BF16).
+ * DLV_EINVAL for an unknown switch or a value the setter refuses, DLV_EUNSUP for features or a window the 16-bit forward refuses. */
 #define DLV_PLAN_NONE (-1)       /* not launched (deconv 3 when upcat_1 is folded) */
 #define DLV_PLAN_ZREG 0          /* conv_zreg_kernel.h: register-resident weights */
 #define DLV_PLAN_DEEP 1          /* conv_deep.hip */

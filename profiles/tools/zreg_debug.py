@@ -1,4 +1,5 @@
-"""debug: one conv block (layer li) through the default z-march build and through variant V; where do they differ?
+"""debug: one conv block (layer li) through the default kernel and under zm_variant V (50: the default by another name,
+51: the LDS-weights z-march conv); where do they differ?
 usage: python profiles/tools/zreg_debug.py [li=1] [D,H,W=40,24,64] [variant=50] [B=1]"""
 import sys
 import numpy as np
@@ -24,9 +25,9 @@ sd = {k.replace("module.", ""): v for k, v in random_state_dict(0).items()}
 wt = sd[CONV_BLOCKS[li] + ".conv.weight"].half().float()
 xin = x1 if x2 is None else torch.cat([x1, x2], 1)
 ref = F.conv3d(xin.cpu(), wt, None, padding=1).numpy()
-eng.set_zm_variant(var)
-out = eng.debug_layer_bf16(2, li, x1, x2, precision="fp16").cpu().numpy()
-eng.set_zm_variant(0)
+eng.diag_set("zm_variant", var)
+out = eng.debug_layer16(2, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy()
+eng.diag_set("zm_variant", 0)
 print("variant", var, "RAW conv: nan", int(np.isnan(out).sum()), "inf", int(np.isinf(out).sum()), "of", out.size)
 d = np.abs(np.nan_to_num(out, nan=1e3, posinf=1e4, neginf=1e4) - ref)
 print("max diff", d.max(), "mean", d.mean(), "ref std", ref.std())
@@ -35,10 +36,10 @@ print("per z:", np.round(d.max(axis=(0, 1, 3, 4)), 2))
 print("per y:", np.round(d.max(axis=(0, 1, 2, 4)), 2))
 print("per x:", np.round(d.max(axis=(0, 1, 2, 3)), 2))
 print("per c:", np.round(d.max(axis=(0, 2, 3, 4)), 2))
-base = eng.debug_layer_bf16(0, li, x1, x2, precision="fp16").cpu().numpy()
-eng.set_zm_variant(var)
-outn = eng.debug_layer_bf16(0, li, x1, x2, precision="fp16").cpu().numpy()
-eng.set_zm_variant(0)
+base = eng.debug_layer16(0, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy()
+eng.diag_set("zm_variant", var)
+outn = eng.debug_layer16(0, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy()
+eng.diag_set("zm_variant", 0)
 dn = np.abs(outn - base)
 print("NORMED vs variant 0: max", dn.max(), "mean", dn.mean(), " per sample max:", np.round(dn.reshape(B, -1).max(1), 3))
 print("RAW per sample max:", np.round(d.reshape(B, -1).max(1), 3))
@@ -54,10 +55,10 @@ m_k, v_k = out.mean(axis=(2, 3, 4)), out.var(axis=(2, 3, 4))
 m_t, v_t = ref.mean(axis=(2, 3, 4)), ref.var(axis=(2, 3, 4))
 print("raw-tensor stats: max |dmean|", np.abs(m_k - m_t).max(), "max |dvar|/var", (np.abs(v_k - v_t) / v_t).max())
 for v in (0, var):
-    eng.set_zm_variant(v)
-    raw = eng.debug_layer_bf16(2, li, x1, x2, precision="fp16").cpu().numpy().astype(np.float64)
-    ssb = eng.debug_layer_bf16(3, li, x1, x2, precision="fp16").cpu().numpy().reshape(-1)[: B * 32 * 2].reshape(B, 32, 2)
-    eng.set_zm_variant(0)
+    eng.diag_set("zm_variant", v)
+    raw = eng.debug_layer16(2, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy().astype(np.float64)
+    ssb = eng.debug_layer16(3, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy().reshape(-1)[: B * 32 * 2].reshape(B, 32, 2)
+    eng.diag_set("zm_variant", 0)
     mean, varr = raw.mean(axis=(2, 3, 4)), raw.var(axis=(2, 3, 4))
     sc = gam.numpy()[None] / np.sqrt(varr + 1e-5)
     shf = bet.numpy()[None] - mean * sc
@@ -65,10 +66,10 @@ for v in (0, var):
     if v == var:
         print("  scale ratio per channel (sample 0):", np.round(ssb[0, :, 0] / sc[0], 4))
 # which rows are missing from the kernel's statistics?  implied variance of variant `var` vs candidate subsets
-eng.set_zm_variant(var)
-raw = eng.debug_layer_bf16(2, li, x1, x2, precision="fp16").cpu().numpy().astype(np.float64)
-ssb = eng.debug_layer_bf16(3, li, x1, x2, precision="fp16").cpu().numpy().reshape(-1)[: B * 32 * 2].reshape(B, 32, 2)
-eng.set_zm_variant(0)
+eng.diag_set("zm_variant", var)
+raw = eng.debug_layer16(2, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy().astype(np.float64)
+ssb = eng.debug_layer16(3, "conv", li, in1=x1, in2=x2, precision="fp16")[0].cpu().numpy().reshape(-1)[: B * 32 * 2].reshape(B, 32, 2)
+eng.diag_set("zm_variant", 0)
 var_k = (gam.numpy()[None] / ssb[..., 0]) ** 2 - 1e-5
 N = D * H * W
 def cand(mask):

@@ -32,7 +32,7 @@ for li, (D, H, W) in ((1, (24, 40, 64)), (1, (64, 64, 64)), (3, (32, 48, 96)), (
         ref = F.mish(F.instance_norm(raw, weight=sd[k + ".adn.N.weight"], bias=sd[k + ".adn.N.bias"], eps=1e-5))
     for algo in ("direct", "winograd"):
         eng.set_conv_algo(algo)
-        out = eng.debug_layer_bf16(0, li, x.cuda(), None, precision="fp16").cpu()
+        out = eng.debug_layer16(0, "conv", li, in1=x.cuda(), precision="fp16")[0].cpu()
         err = (out - ref).abs()
         print(f"conv block {li} {D}x{H}x{W} [{algo}]: max abs err {float(err.max()):.3e}  mean {float(err.mean()):.3e}", flush=True)
 vol = synth_volume_torch(shape, 1, eng.device, dense=True)

@@ -1,5 +1,5 @@
-"""A/B of the z-march conv builds inside one process (same device, interleaved rounds): per-kernel HIP-event times on a
-dense volume of 128^3 windows (one lane), and the difference of the blended logits between the builds.
+"""A/B of the "zm_variant" switch (0 / 50: default, 51: the LDS-weights z-march conv for the z-reg layers) inside one
+process (same device, interleaved rounds): per-kernel HIP-event times on a dense volume of 128^3 windows (one lane), and the difference of the blended logits between the builds.
 usage: python profiles/zreg_ab.py [variants, default "0,50"] [rounds, default 3] [Z,Y,X, default 256,256,512]"""
 import json
 import sys
@@ -25,7 +25,7 @@ roi = (128, 128, 128)
 res, accs = {}, {}
 for rnd in range(rounds + 1):  # round 0 = warm-up
     for v in variants:
-        eng.set_zm_variant(v)
+        eng.diag_set("zm_variant", v)
         acc = torch.zeros(shape, dtype=torch.float32, device="cuda")
         eng.prof_reset()
         eng.prof_enable(True)

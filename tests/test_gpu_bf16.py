@@ -1,4 +1,4 @@
-"""bf16 MFMA path vs the oracle: every kernel in isolation (dlv_debug_layer_bf16), the whole
+"""bf16 MFMA path vs the oracle: every kernel in isolation (dlv_debug_layer16), the whole
 forward, and the fused sliding-window pass.  Tolerances are the bf16 ones stated in DESIGN.md:
 activations/weights carry 8 significant bits, accumulation and InstanceNorm statistics are fp32."""
 import numpy as np
@@ -274,37 +274,25 @@ def test_sw_pass_fp16_matches_fp32_engine(eng, golden_dir):
 
 
 # ---------------------------------------------------------------------------------------------------
-# opt-in builds of the z-march conv (dlv_debug_set_zm_variant): same torch reference, same tolerance
+# the "zm_variant" switch (dlv_diag_set): same torch reference, same tolerance
 # ---------------------------------------------------------------------------------------------------
-def _diag_lib():
-    import os
-
-    return "diag" in os.environ.get("DLV_LIB", "")
-
-
 def test_product_library_refuses_the_diagnostic_zmarch_builds(eng):
-    """ONE test for all of them: the experimental / stamped / timing-only builds (6, 11, 20, 24, 40, ...) live in
-    libdelivr_hip_diag.so only; the product library refuses to select them (and ignores DLV_ZM_VARIANT), so no setting can
-    reach a wrong-result kernel."""
+    """ONE test for all of them: the experimental / stamped / timing-only builds (6, 11, 20, 24, 40, ...) of the z-march conv
+    were retired; the library refuses to select them, so no setting can reach a wrong-result kernel."""
     from delivr_cfos_amd._lib import DelivrHipError
 
-    if _diag_lib():
-        pytest.skip("diagnostic library loaded")
     for variant in (3, 4, 6, 11, 12, 13, 20, 24, 30, 40, 41, 45):
         with pytest.raises(DelivrHipError):
-            eng.set_zm_variant(variant)
-    eng.set_zm_variant(0)
+            eng.diag_set("zm_variant", variant)
+    eng.diag_set("zm_variant", 0)
 
 
-# the variants a run can execute: 50 / 51 in the product library, the A/B builds too with DLV_LIB=libdelivr_hip_diag.so
-@pytest.mark.parametrize("variant", [50, 51] + ([6, 11, 20, 24, 40] if _diag_lib() else []))
+@pytest.mark.parametrize("variant", [50, 51])
 @pytest.mark.parametrize("li,c1,c2,prec", [(1, 32, 0, "fp16"), (16, 32, 32, "fp16"), (1, 32, 0, "bf16"), (16, 32, 32, "bf16")])
 def test_zmarch_variants(eng, net, variant, li, c1, c2, prec):
-    """Register-resident-weights conv (50 = the default) and the LDS-resident-weights kernel (51) in the product library;
-    with DLV_LIB=libdelivr_hip_diag.so also the streaming-store (6), double-buffered half-plane (20), LDS-DMA (24) and software-pipelined (40) builds of the
+    """Register-resident-weights conv (50 = the default) and the LDS-resident-weights kernel (51) on the
     32->32 / 64->32 conv block on a 40x24x64 window (3 z chunks of 16, an in-plane tile grid of 3x2, ragged z tail):
-    against conv3d+InstanceNorm+Mish in fp32 on the same 16-bit-rounded operands.  Variant 40 drops the conv bias
-    (InstanceNorm cancels it) and takes the statistics on the rounded values: same tolerance."""
+    against conv3d+InstanceNorm+Mish in fp32 on the same 16-bit-rounded operands."""
     import torch
     import torch.nn.functional as F
 
@@ -318,14 +306,12 @@ def test_zmarch_variants(eng, net, variant, li, c1, c2, prec):
     with torch.no_grad():
         raw = F.conv3d(xin, rnd(blk.conv.weight), blk.conv.bias, padding=1)
         ref = F.mish(F.instance_norm(raw, weight=blk.adn.N.weight, bias=blk.adn.N.bias, eps=1e-5))
-    if variant == 11:
-        return  # timing-only build (no epilogue): wrong results by construction, diagnostic library only
     try:
-        eng.set_zm_variant(variant)
-        out = eng.debug_layer_bf16(0, li, x1.cuda(), None if x2 is None else x2.cuda(), precision=prec).cpu()
+        eng.diag_set("zm_variant", variant)
+        out = eng.debug_layer16(0, "conv", li, in1=x1.cuda(), in2=None if x2 is None else x2.cuda(), precision=prec)[0].cpu()
     finally:
-        eng.set_zm_variant(0)
-    base = eng.debug_layer_bf16(0, li, x1.cuda(), None if x2 is None else x2.cuda(), precision=prec).cpu()
+        eng.diag_set("zm_variant", 0)
+    base = eng.debug_layer16(0, "conv", li, in1=x1.cuda(), in2=None if x2 is None else x2.cuda(), precision=prec)[0].cpu()
     err = (out - ref).abs()
     tol_max, tol_mean = (0.01, 1e-3) if prec == "fp16" else (0.06, 6e-3)
     assert err.max() < tol_max, float(err.max())

@@ -153,6 +153,26 @@ def test_unknown_switch_is_refused(layer_plan):
         layer_plan((64, 64, 64), {"no_such_switch": 1})
 
 
+def test_zm_variant_takes_0_50_and_51_only(layer_plan):
+    """the numbers that selected the retired experiment builds of the z-march conv are refused by the planner as dlv_diag_set
+    refuses them; 50 is the default by another name, 51 gives every z-reg layer to the LDS-weights z-march conv"""
+    from delivr_cfos_amd._lib import DelivrHipError
+
+    for v in (3, 4, 6, 11, 12, 13, 20, 24, 25, 30, 31, 40, 45, 1, -1, 52):
+        with pytest.raises(DelivrHipError):
+            layer_plan((128, 128, 128), {"zm_variant": v})
+    default = layer_plan((128, 128, 128), {"zm_variant": 0})
+    assert default == layer_plan((128, 128, 128))
+    assert layer_plan((128, 128, 128), {"zm_variant": 50}) == default
+    lds = layer_plan((128, 128, 128), {"zm_variant": 51})
+    zreg = [li for li in range(18) if default["conv"][li]["kernel"] == "ZREG"]
+    assert zreg == [1, 2, 3, 14, 15, 16, 17]
+    for li in range(1, 18):
+        assert lds["conv"][li]["kernel"] == ("ZMARCH" if li in zreg else default["conv"][li]["kernel"]), li
+    assert not any(c["folded"] or c["act_on_load"] for c in lds["conv"])
+    assert any(l.startswith("conv3_zmarch_f16_c64x32_d128") for l, _, _ in lds["labels"])  # (upcat_1 unfolded: 32 + 32 channels)
+
+
 def test_layer_plan_header_is_plain_host_code():
     """layer_plan.h compiles as C++17 on the host alone: no HIP header, nothing of the context"""
     cxx = shutil.which("clang++") or shutil.which("g++") or ("/opt/rocm/llvm/bin/clang++" if os.path.isfile("/opt/rocm/llvm/bin/clang++") else None)

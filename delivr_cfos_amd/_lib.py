@@ -244,6 +244,8 @@ SIGNATURES = {
     "dlv_cc_runs_decode_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, _P, _P, C.c_uint64, _P]),
     "dlv_paint_owner_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, _P]),
     "dlv_paint_apply_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_int, _P]),
+    "dlv_paint_labels_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P]),
+    "dlv_paint_runs_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, _P]),
     "dlv_edt_u16_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P]),
     "dlv_heatmap_counts_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.c_int, _P]),
     "dlv_gauss_blur_f32_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),

@@ -6,6 +6,8 @@
 // re-color other blobs close by") - times bin_img.  Restated order-free: owner[v] = max{ i+1 : box_i contains v },
 // built with atomicMax by one wave per box (boxes are tiny: a cell is 10-40 voxels), then IMG[v] = bin[v] * value[owner[v]-1].
 // Integer only; identical to the sequential loop for any box list (tests/test_gpu_parity.py, tests/golden/ref_paint.npz).
+// The opt-in painting by label instead of by box - out[v] = value[label[v]], from the dense labels or their run-length coding - is
+// cc_paint.hip (settings["mi355x"]["paint_from"] = "labels").
 #include "common.h"
 
 // scipy-exact fp64 arithmetic below (Gaussian filter, distance transform): no a*b+c may become an fma - HIP contracts by

@@ -963,6 +963,92 @@ class HipEngine:
         self.sync()
         return outs
 
+    def _paint_luts(self, what: str, rgb, u16):
+        """the look-up tables of paint_labels / paint_runs in HBM -> (n_lut, packed r | g << 8 | b << 16 int32 tensor or None, uint16
+        tensor or None)"""
+        torch = self.torch
+        if rgb is None and u16 is None:
+            raise ValueError(f"{what}: neither rgb nor u16 is given")
+        n_lut, rgb_dev, u16_dev = None, None, None
+        if rgb is not None:
+            rgb = np.asarray(rgb)
+            if rgb.dtype != np.uint8 or rgb.ndim != 2 or rgb.shape[1] != 3 or rgb.shape[0] < 1:
+                raise TypeError(f"{what}: rgb: expected an (n_lut, 3) uint8 array, got {rgb.dtype} of shape {rgb.shape}")
+            n_lut = int(rgb.shape[0])
+            wide = rgb.astype(np.uint32)
+            packed = np.ascontiguousarray(wide[:, 0] | (wide[:, 1] << 8) | (wide[:, 2] << 16))
+            rgb_dev = torch.from_numpy(packed.view(np.int32)).to(self.device)
+        if u16 is not None:
+            u16 = np.ascontiguousarray(u16)
+            if u16.dtype != np.uint16 or u16.ndim != 1 or u16.shape[0] < 1:
+                raise TypeError(f"{what}: u16: expected an (n_lut,) uint16 array, got {u16.dtype} of shape {u16.shape}")
+            if n_lut is not None and int(u16.shape[0]) != n_lut:
+                raise ValueError(f"{what}: rgb holds {n_lut} entries, u16 {int(u16.shape[0])}")
+            n_lut = int(u16.shape[0])
+            u16_dev = torch.from_numpy(u16.view(np.int16).copy()).to(self.device)
+        return n_lut, rgb_dev, u16_dev
+
+    def _paint_planes(self, shape, rgb_dev, u16_dev):
+        """the output planes of one paint call (not cleared: the kernels write every element) and their pointers, NULL where a
+        table is absent"""
+        torch = self.torch
+        chans = tuple(torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(3)) if rgb_dev is not None else None
+        gray = torch.empty(shape, dtype=torch.uint16, device=self.device) if u16_dev is not None else None
+        ptrs = [C.c_void_p(t.data_ptr()) for t in chans] if chans else [None, None, None]
+        ptrs.append(C.c_void_p(gray.data_ptr()) if gray is not None else None)
+        result = tuple(x for x in (chans, gray) if x is not None)
+        return ptrs, (result[0] if len(result) == 1 else result)
+
+    def paint_labels(self, labels, rgb=None, u16=None):
+        """Every voxel painted with the value of the cell whose label it carries, out[v] = lut[labels[v]] (dlv_paint_labels_dev;
+        blob_highlighter's "labels" mode).  labels: int32 (uint32 payload) (Z,Y,X) in HBM, contiguous.  rgb: (n_lut, 3) uint8,
+        u16: (n_lut,) uint16, indexed by label - either or both, written in one pass; label 0 and labels >= n_lut paint 0.
+        -> (r, g, b) uint8 tensors for rgb, a uint16 tensor for u16, ((r, g, b), image) for both - in HBM."""
+        Z, Y, X = self._label_volume("paint_labels", labels)
+        n_lut, rgb_dev, u16_dev = self._paint_luts("paint_labels", rgb, u16)
+        ptrs, result = self._paint_planes((Z, Y, X), rgb_dev, u16_dev)
+        self._enter()
+        try:
+            self._check(self.lib.dlv_paint_labels_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n_lut,
+                                                      C.c_void_p(rgb_dev.data_ptr()) if rgb_dev is not None else None,
+                                                      C.c_void_p(u16_dev.data_ptr()) if u16_dev is not None else None, *ptrs))
+        finally:
+            self._leave()
+        return result
+
+    def paint_runs(self, runs: dict, z0: int = 0, z1: Optional[int] = None, rgb=None, u16=None):
+        """paint_labels for the planes [z0, z1) of the label volume a run-length coding holds, straight from the runs: the label
+        volume is never built (dlv_paint_runs_dev).  runs: the dict of cc_runs_encode / label_runs.load_runs (validated there: the
+        kernel clamps what it reads, it does not judge it).  Only the rows' slice of row_start and their runs are uploaded, as
+        cc_runs_decode does.  -> the planes of paint_labels, (z1 - z0, Y, X) each, every element written."""
+        torch = self.torch
+        Z, Y, X = (int(v) for v in runs["shape"])
+        z0, z1 = int(z0), Z if z1 is None else int(z1)
+        if not 0 <= z0 < z1 <= Z:
+            raise ValueError(f"paint_runs: planes [{z0}, {z1}) do not lie in the {Z} planes of the coding")
+        rs = np.ascontiguousarray(runs["row_start"][z0 * Y:z1 * Y + 1], dtype=np.uint64)
+        a, b = int(rs[0]), int(rs[-1])
+        if len(rs) != (z1 - z0) * Y + 1 or not a <= b <= min(len(runs[k]) for k in ("x0", "x1", "label")):
+            raise ValueError("paint_runs: row_start does not match the shape and the run arrays")
+        n_lut, rgb_dev, u16_dev = self._paint_luts("paint_runs", rgb, u16)
+
+        def dev(arr, np_dtype, as_int):  # (unsigned payloads in torch's signed types)
+            return torch.from_numpy(np.ascontiguousarray(arr, dtype=np_dtype).view(as_int)).to(self.device)
+
+        rs_dev = dev(rs, np.uint64, np.int64)
+        x0, x1 = dev(runs["x0"][a:b], np.uint16, np.int16), dev(runs["x1"][a:b], np.uint16, np.int16)
+        label = dev(runs["label"][a:b], np.uint32, np.int32)
+        ptrs, result = self._paint_planes((z1 - z0, Y, X), rgb_dev, u16_dev)
+        self._enter()
+        try:
+            self._check(self.lib.dlv_paint_runs_dev(self.ctx, C.c_void_p(rs_dev.data_ptr()), (z1 - z0) * Y, X,
+                                                    *(C.c_void_p(t.data_ptr()) if b > a else None for t in (x0, x1, label)), b - a,
+                                                    n_lut, C.c_void_p(rgb_dev.data_ptr()) if rgb_dev is not None else None,
+                                                    C.c_void_p(u16_dev.data_ptr()) if u16_dev is not None else None, *ptrs))
+        finally:
+            self._leave()  # (torch's stream now waits for the kernel: the uploaded runs freed here are not reused before it)
+        return result
+
     # ---- atlas-space heat map ----------------------------------------------------------------------
     def heatmap(self, cells_xyz: np.ndarray, shape_zyx, sigma: float = 2.25):
         """create_heatmap (cells_to_atlas.py:174-200) on the device: float32 (Z,Y,X) tensor in HBM."""

@@ -676,6 +676,42 @@ def padded_boxes(bounding_boxes: np.ndarray, cc_ids, shape_zyx, times: int = 1) 
     return out.astype(np.int32)
 
 
+PAINT_SOURCES = ("boxes", "labels")
+
+
+def paint_source(settings) -> str:
+    """settings["mi355x"]["paint_from"]: "boxes" (or absent) - the reference's painting of padded bounding boxes times binaries.npy;
+    "labels" - every voxel gets the value of the cell whose label it carries (blob_highlighter's docstring).  ValueError for
+    anything else."""
+    value = ((settings or {}).get("mi355x") or {}).get("paint_from")
+    if value is None:
+        return "boxes"
+    if not isinstance(value, str) or value not in PAINT_SOURCES:
+        raise ValueError(f"settings['mi355x']['paint_from'] = {value!r}: expected \"boxes\" (the default: the reference's padded "
+                         "bounding boxes) or \"labels\" (each voxel coloured by its own label)")
+    return value
+
+
+def paint_luts(ids, red, green, blue, graph_order, n: int):
+    """The look-up tables of the "labels" painting for a label volume with the labels 1..n: rgb (n + 1, 3) uint8 and region
+    (n + 1,) uint16, indexed by label.  connected_component_id IS the label (the box path indexes stats["bounding_boxes"][id], which
+    cc3d indexes by label); a label without a row of the cell table keeps 0, and so does entry 0, the background.  The values wrap
+    into their type as the box path's .astype does.  ValueError for an id of 0, IndexError for an id above n (the box path's
+    "beyond the statistics table"); blob_highlighter has refused duplicate ids before."""
+    ids = np.asarray(ids, dtype=np.int64)
+    n = int(n)
+    if ids.size and int(ids.min()) < 1:
+        raise ValueError(f"connected_component_id {int(ids.min())}: label 0 is the background, a cell's label is 1..{n}")
+    if ids.size and int(ids.max()) > n:
+        raise IndexError(f"connected_component_id {int(ids.max())} beyond the {n} labels of the label volume")
+    rgb = np.zeros((n + 1, 3), dtype=np.uint8)
+    region = np.zeros(n + 1, dtype=np.uint16)
+    for c, col in enumerate((red, green, blue)):
+        rgb[ids, c] = np.asarray(col).astype(np.uint8)
+    region[ids] = np.asarray(graph_order).astype(np.uint16)
+    return rgb, region
+
+
 def max_window_multiplicity(starts, roi) -> int:
     """Largest number of windows covering one voxel, for the (n,3) window starts of the reference's enumeration
     (inference/sliding_window_inferer.py:143-145) and the window size: the peak of the count map after one pass."""

@@ -421,6 +421,26 @@ int dlv_paint_owner_dev(dlv_ctx* ctx, const uint8_t* bin_dev, int Z, int Y, int 
                         const int32_t* boxes_host, uint64_t n_boxes, uint32_t* owner_dev);
 int dlv_paint_apply_dev(dlv_ctx* ctx, const uint32_t* owner_dev, const uint8_t* bin_dev, uint64_t nvox,
                         const void* values_dev, int elem_bytes, void* out_dev);
+/* Painting from the labels (csrc/cc_paint.hip; blob_highlighter with settings["mi355x"]["paint_from"] = "labels"). Replaces the same
+ * two loops, with their stated intent in place of their boxes: every voxel gets the value of the cell whose label it carries,
+ * out[v] = lut[label[v]], and 0 elsewhere - no box, no padding, no "might accidentally re-color other blobs close by". The look-up
+ * tables are indexed by label, n_lut entries each, entry 0 the background: lut_rgb_dev uint32 = r | g << 8 | b << 16 with the three
+ * uint8 planes out_r / out_g / out_b (all three or none), lut_u16_dev uint16 with the plane out_u16; either pair may be NULL, and
+ * one pass over the labels or the runs writes every plane asked for. A label of 0 writes 0 and so does a label >= n_lut: the
+ * kernels clamp, they do not judge.
+ *  dlv_paint_labels_dev: the labels are the dense uint32 volume (Z,Y,X), contiguous.
+ *  dlv_paint_runs_dev: the labels are the run-length coding of dlv_cc_runs_emit_dev, addressed as dlv_cc_runs_decode_dev addresses
+ *    it: rows [0, n_rows) of row length X, row_start_dev (n_rows + 1 entries) rebased by its first one, run indices clamped to n_runs
+ *    (x0 / x1 / label may be NULL with n_runs == 0), a run clamped to its row. The label volume is never built.
+ * Every element of every output row is written exactly once, zeros included: the planes need not be cleared. Integer work only,
+ * one writer per element, no atomics: exact. DLV_EINVAL, with nothing written, for: neither table; a table without its planes or
+ * planes without their table (the three byte planes count as one); a pointer not aligned to its element; a NULL ctx / labels /
+ * row_start, an empty volume or n_lut < 1. X above 65536 in dlv_paint_runs_dev: DLV_EUNSUP. Asynchronous on the context's stream. */
+int dlv_paint_labels_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n_lut, const uint32_t* lut_rgb_dev,
+                         const uint16_t* lut_u16_dev, uint8_t* out_r, uint8_t* out_g, uint8_t* out_b, uint16_t* out_u16);
+int dlv_paint_runs_dev(dlv_ctx* ctx, const uint64_t* row_start_dev, uint64_t n_rows, int X, const uint16_t* x0_dev,
+                       const uint16_t* x1_dev, const uint32_t* label_dev, uint64_t n_runs, uint64_t n_lut, const uint32_t* lut_rgb_dev,
+                       const uint16_t* lut_u16_dev, uint8_t* out_r, uint8_t* out_g, uint8_t* out_b, uint16_t* out_u16);
 
 /* Depth-coded blob map (blob_depthmap.py:160-170): scipy.ndimage.distance_transform_edt(np.pad(stack, 1), sampling)
  * [1:-1,1:-1,1:-1].astype(np.uint16) of the down-sampled masked stack - the distance (in the units of `sampling_zyx`, 3

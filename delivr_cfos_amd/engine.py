@@ -918,6 +918,54 @@ class HipEngine:
             self._leave()  # (torch's stream now waits for the kernel: the uploaded runs freed here are not reused before it)
         return out
 
+    def cc_overlap(self, labels_a, n_a: int, labels_b, n_b: int, settings=None) -> dict:
+        """The overlap table of two label volumes in HBM (dlv_cc_overlap_count_dev, dlv_cc_overlap_dev; the numpy statement:
+        compare_cells.overlap_table_np).  labels_a, labels_b: int32 (uint32 payload) (Z,Y,X) in HBM, contiguous, of one shape.  A
+        voxel takes part when 1 <= a <= n_a and 1 <= b <= n_b.  -> {"a", "b": uint32 (P), "voxels": uint64 (P), "segments": S}: the
+        P pairs of labels that share voxels, sorted by (a, b) and unique, with the voxels they share; S = the stretches of one pair
+        inside the rows, which sized the table.  The table (32 bytes per min(S, n_a * n_b), rounded up to a power of two) and the
+        outputs (16 bytes each) must fit the HBM budget (streaming.hbm_budget_bytes of `settings`): MemoryError names the sizes."""
+        torch = self.torch
+        shape = self._label_volume("cc_overlap", labels_a)
+        if self._label_volume("cc_overlap", labels_b) != shape:
+            raise ValueError(f"cc_overlap: labels_a of shape {shape}, labels_b of shape {tuple(labels_b.shape)}")
+        Z, Y, X = shape
+        n_a, n_b = int(n_a), int(n_b)
+        if n_a < 0 or n_b < 0:
+            raise ValueError(f"cc_overlap: n_a = {n_a}, n_b = {n_b}")
+        empty = {"a": np.zeros(0, dtype=np.uint32), "b": np.zeros(0, dtype=np.uint32), "voxels": np.zeros(0, dtype=np.uint64), "segments": 0}
+        pa, pb = C.c_void_p(labels_a.data_ptr()), C.c_void_p(labels_b.data_ptr())
+        s, p = C.c_uint64(), C.c_uint64()
+        self._enter()
+        try:
+            self._check(self.lib.dlv_cc_overlap_count_dev(self.ctx, pa, pb, Z, Y, X, n_a, n_b, C.byref(s)))
+            S = int(s.value)
+            bound = min(S, n_a * n_b)
+            if bound == 0:
+                return empty
+            cap = 1 << (2 * bound - 1).bit_length()  # the power of two >= 2 * bound
+            from .streaming import hbm_budget_bytes
+
+            need, budget = cap * 16 + 2 * bound * 8, hbm_budget_bytes(self, settings)
+            if need > budget:
+                raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): cc_overlap needs a pair table of {cap} slots ({cap * 16 / 2**30:.2f} GiB) and "
+                                  f"outputs of {bound} pairs ({bound * 16 / 2**30:.2f} GiB) for {S} pair segments of {n_a} x {n_b} labels, "
+                                  f"the HBM budget is {budget / 2**30:.2f} GiB; compare a crop, or raise settings['mi355x']['hbm_budget_gb']")
+            table = torch.empty(2 * cap, dtype=torch.int64, device=self.device)  # uint64 payloads
+            keys = torch.empty(bound, dtype=torch.int64, device=self.device)
+            voxels = torch.empty(bound, dtype=torch.int64, device=self.device)
+            self._check(self.lib.dlv_cc_overlap_dev(self.ctx, pa, pb, Z, Y, X, n_a, n_b, S, C.c_void_p(table.data_ptr()), cap,
+                                                    C.c_void_p(keys.data_ptr()), C.c_void_p(voxels.data_ptr()), bound, C.byref(p)))
+        finally:
+            self._leave()
+        P = int(p.value)
+        key = keys[:P].cpu().numpy().view(np.uint64)
+        vox = voxels[:P].cpu().numpy().view(np.uint64)
+        order = np.argsort(key, kind="stable")  # (the device order is unspecified)
+        key = key[order]
+        return {"a": (key >> np.uint64(32)).astype(np.uint32), "b": (key & np.uint64(0xFFFFFFFF)).astype(np.uint32),
+                "voxels": np.ascontiguousarray(vox[order]), "segments": S}
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

@@ -386,6 +386,26 @@ int dlv_cc_runs_emit_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y,
                          uint16_t* x0_dev, uint16_t* x1_dev, uint32_t* label_dev);
 int dlv_cc_runs_decode_dev(dlv_ctx* ctx, const uint64_t* row_start_dev, uint64_t n_rows, int X, const uint16_t* x0_dev,
                            const uint16_t* x1_dev, const uint32_t* label_dev, uint64_t n_runs, uint32_t* labels_out_dev);
+/* The overlap table of two label volumes (no counterpart in the reference; csrc/cc_overlap.hip, delivr_cfos_amd/compare_cells.py): every
+ * pair of labels (a, b) that share voxels, with the number of voxels they share. a_dev, b_dev: uint32 (Z,Y,X) contiguous, 4-byte
+ * aligned, labels below 2^32 - 1. A voxel takes part when 1 <= a <= n_a and 1 <= b <= n_b: the background and labels above n in either
+ * volume contribute nothing. The key of a pair is (a << 32) | b. A pair segment is a maximal stretch of one key inside a row (z, y).
+ *  dlv_cc_overlap_count_dev: *n_segments = the pair segments S of the volumes, on the host. The distinct pairs P are at most
+ *    min(S, n_a * n_b). Synchronous.
+ *  dlv_cc_overlap_dev: with the S of the count on the same volumes, the P distinct keys go to keys_out_dev[0..P) and their voxels to
+ *    voxels_out_dev[0..P) (uint64 each, out_cap >= min(S, n_a * n_b) entries, 8-byte aligned), *n_pairs = P on the host. table_dev: the
+ *    caller's scratch of cap slots of 16 bytes (2 * cap uint64, 16-byte aligned), cap a power of two >= 2 * min(S, n_a * n_b); the call
+ *    clears it. The order of the pairs on the device is unspecified (HipEngine.cc_overlap sorts by key on the host); the pairs and their
+ *    voxels are exact and independent of scheduling: integer work only. With S = 0 nothing is launched and P = 0. Synchronous.
+ * DLV_EINVAL, checked on the host before anything is launched and with nothing written: a NULL pointer, a misaligned pointer,
+ * Z/Y/X < 1, n_a or n_b above 2^32 - 2, cap not a power of two or below 2 * min(S, n_a * n_b), out_cap below min(S, n_a * n_b). X above
+ * 2^30: DLV_EUNSUP. DLV_ESTATE with a message that names the table: a key found no slot, or more pairs than out_cap - the kernels bound
+ * every probe by cap and every write by out_cap, and neither happens when S is the count of these volumes. */
+int dlv_cc_overlap_count_dev(dlv_ctx* ctx, const uint32_t* a_dev, const uint32_t* b_dev, int Z, int Y, int X, uint64_t n_a, uint64_t n_b,
+                             uint64_t* n_segments);
+int dlv_cc_overlap_dev(dlv_ctx* ctx, const uint32_t* a_dev, const uint32_t* b_dev, int Z, int Y, int X, uint64_t n_a, uint64_t n_b,
+                       uint64_t n_segments, uint64_t* table_dev, uint64_t cap, uint64_t* keys_out_dev, uint64_t* voxels_out_dev,
+                       uint64_t out_cap, uint64_t* n_pairs);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack

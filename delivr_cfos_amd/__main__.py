@@ -90,7 +90,7 @@ def main(argv=None) -> int:
                               tta=flags["TEST_TIME_AUGMENTATION"], comment=brain, load_all_ram=flags["LOAD_ALL_RAM"],
                               settings=settings, prefetch=nxt[0] if nxt else None, defer_write=True)
         finally:
-            hostio.wait_deferred()  # every binaries.npy is complete before the next step reads it
+            hostio.wait_deferred()  # every binaries.npy - and network_output.npy - is complete before the next step reads it
     if flags.get("POSTPROCESSING"):
         step_no += 1
         from .count_blobs import count_blobs

@@ -233,6 +233,7 @@ SIGNATURES = {
     "dlv_cc_counts_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P]),
     "dlv_cc_size_filter_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]),
     "dlv_cc_intensity_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_uint64, _P, _P, _P, _P]),
+    "dlv_cc_confidence_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "dlv_cc_quantiles_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.POINTER(C.c_int),
                                        _P, _P]),
     "dlv_cc_shell_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P]),

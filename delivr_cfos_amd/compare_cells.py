@@ -7,11 +7,16 @@ The overlap table of the label volumes A (labels 1..n_a) and B (1..n_b) of one s
 1 <= a <= n_a and 1 <= b <= n_b - the background and labels above n contribute nothing -, and the table lists every pair (a, b)
 among them with the number of voxels that hold it, sorted by (a, b).  overlap_table_np is that definition in numpy.
 
-    python -m delivr_cfos_amd.compare_cells PRED REF --out DIR [--name N] [--min-iou T] [--device I]
+    python -m delivr_cfos_amd.compare_cells PRED REF --out DIR [--name N] [--min-iou T] [--device I] [--scores PICKLE [--score-key KEY]]
 
 PRED / REF: a uint8 mask .npy (binaries.npy, or an annotation saved the same way: labelled 26-connected as count_blobs labels), a
 dense uint16 / uint32 label .npy (<brain>-<N>-cc3d.npy), or a run-length label file (<brain>-<N>-cc3d.runs).  Prints the summary as
 one JSON line and writes <name>-pairs.csv, <name>-pred.csv, <name>-ref.csv and <name>-summary.json into DIR.
+
+With a score per prediction cell - count_blobs' confidence_max of settings["mi355x"]["confidence_stats"], the threshold above which the
+cell disappears - the same table gives the whole precision / recall curve (score_curve): --scores names the prediction's
+<brain>-stats.pickle, --score-key the column (default confidence_max); <name>-curve.csv is written beside the others and the summary
+gains average_precision, best_f1 and best_f1_score.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ from . import label_runs
 MAX_LABEL = label_runs.MAX_LABEL
 CELL_COLUMNS = ("id", "voxels", "partners", "best", "best_voxels", "best_iou", "matched")
 PAIR_COLUMNS = ("pred", "ref", "voxels", "iou")
+CURVE_COLUMNS = ("score", "kept", "true_pred", "detected_ref", "precision", "recall", "f1")
 
 
 def _as_unsigned(labels, what):
@@ -150,6 +156,75 @@ def match_cells(table: dict, counts_a, counts_b, min_iou: float = 0.0) -> dict:
     return {"pairs": {"pred": a, "ref": b, "voxels": vox, "iou": iou, "hit": hit}, "pred": pred, "ref": ref, "summary": summary}
 
 
+def _checked_scores(scores, n_pred=None) -> np.ndarray:
+    """one finite number per prediction cell as float64, row 0 of a table of n_pred + 1 rows dropped; with n_pred None the length is
+    not judged yet (compare_cells looks at the values before it opens a volume)"""
+    try:
+        s = np.asarray(scores).astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("score_curve: scores: expected one number per prediction cell") from None
+    if s.ndim != 1 or not np.isfinite(s).all():
+        raise ValueError(f"score_curve: scores of shape {s.shape}: expected a 1-D array of finite numbers (no NaN, no inf)")
+    if n_pred is None:
+        return s
+    if len(s) not in (n_pred, n_pred + 1):
+        raise ValueError(f"score_curve: {len(s)} scores beside {n_pred} prediction cells: expected {n_pred}, or {n_pred + 1} with a row 0")
+    return s[1:] if len(s) == n_pred + 1 else s
+
+
+def score_curve(matched: dict, scores) -> dict:
+    """The detection curve of a comparison over a score per prediction cell.  matched: match_cells' dict; scores: one finite number
+    per prediction cell 1..n_pred (or n_pred + 1 numbers, row 0 ignored) - ValueError for NaN, inf or another length.  For every
+    distinct score t, descending: kept = the cells with score >= t, true_pred = the kept cells with a hit pair, detected_ref = the
+    reference cells with a hit pair whose prediction cell is kept, precision = true_pred / kept, recall = detected_ref / n_ref, f1 as
+    in match_cells.
+    -> {"curve": {"score": float64, "kept", "true_pred", "detected_ref": int64, "precision", "recall", "f1": float64}, one row per
+        cut - an undefined ratio (recall without a reference cell, f1 without both or with precision + recall == 0) is NaN here and
+        null in the file -,
+        "summary": average_precision = sum_k (recall_k - recall_{k-1}) * precision_k with recall_0 = 0 (None when n_ref == 0),
+        best_f1 and best_f1_score = the largest f1 and its cut, the highest cut on a tie (None without a defined f1)}."""
+    n_pred, n_ref = int(matched["summary"]["n_pred"]), int(matched["summary"]["n_ref"])
+    s = _checked_scores(scores, n_pred)
+    pairs = matched["pairs"]
+    hit = np.asarray(pairs["hit"], dtype=bool)
+    a, b = np.asarray(pairs["pred"], dtype=np.int64)[hit], np.asarray(pairs["ref"], dtype=np.int64)[hit]
+    cuts = np.unique(s)[::-1]
+    ascending = np.sort(s)
+    kept = (n_pred - np.searchsorted(ascending, cuts, side="left")).astype(np.int64)
+    true_scores = np.sort(s[np.unique(a) - 1])  # the cells with a hit pair
+    true_pred = (len(true_scores) - np.searchsorted(true_scores, cuts, side="left")).astype(np.int64)
+    # a reference cell is detected from its best-scored hit partner down
+    ref_best = np.full(n_ref, -np.inf, dtype=np.float64)
+    np.maximum.at(ref_best, b - 1, s[a - 1])
+    ref_scores = np.sort(ref_best[np.isfinite(ref_best)])
+    detected = (len(ref_scores) - np.searchsorted(ref_scores, cuts, side="left")).astype(np.int64)
+    precision = true_pred.astype(np.float64) / kept.astype(np.float64)  # (a cut is some cell's score: kept >= 1)
+    recall = detected.astype(np.float64) / float(n_ref) if n_ref else np.full(len(cuts), np.nan)
+    f1 = np.full(len(cuts), np.nan)
+    ok = np.isfinite(recall) & (precision + np.nan_to_num(recall) > 0)
+    f1[ok] = 2 * precision[ok] * recall[ok] / (precision[ok] + recall[ok])
+    ap = None if n_ref == 0 else float(np.sum(np.diff(recall, prepend=0.0) * precision))
+    best = int(np.nanargmax(f1)) if np.isfinite(f1).any() else None  # (the first of equal maxima: the highest cut)
+    summary = {"average_precision": ap, "best_f1": None if best is None else float(f1[best]),
+               "best_f1_score": None if best is None else float(cuts[best])}
+    return {"curve": {"score": cuts.astype(np.float64), "kept": kept, "true_pred": true_pred, "detected_ref": detected,
+                      "precision": precision, "recall": recall, "f1": f1}, "summary": summary}
+
+
+def _open_scores(scores, score_key: str):
+    """compare_cells' scores: an array, or the path of a <brain>-stats.pickle whose entry score_key is the column"""
+    if isinstance(scores, (str, os.PathLike)):
+        import pickle
+
+        with open(os.fspath(scores), "rb") as fh:
+            stats = pickle.load(fh)
+        if not isinstance(stats, dict) or score_key not in stats:
+            raise ValueError(f"compare_cells: {os.fspath(scores)} holds no entry {score_key!r} (count_blobs writes confidence_max with "
+                             "settings['mi355x']['confidence_stats'])")
+        scores = stats[score_key]
+    return _checked_scores(scores)
+
+
 # ---- the sources ---------------------------------------------------------------------------------------------------------------
 def _count_in_name(path: str):
     """N of a <brain>-<N>-cc3d.npy name, None for any other name"""
@@ -227,6 +302,13 @@ def _field(v) -> str:
     return str(int(v))
 
 
+def _curve_csv(curve: dict) -> str:
+    rows = [",".join(CURVE_COLUMNS)]
+    rows += [",".join("null" if isinstance(v, float) and math.isnan(v) else _field(v) for v in row)
+             for row in zip(*(curve[c].tolist() for c in CURVE_COLUMNS))]
+    return "\n".join(rows) + "\n"
+
+
 def _csv(columns, table: dict) -> str:
     rows = [",".join(columns)]
     rows += [",".join(_field(v) for v in row) for row in zip(*(table[c].tolist() for c in columns))]
@@ -235,8 +317,11 @@ def _csv(columns, table: dict) -> str:
 
 def result_files(result: dict, name: str = "compare") -> dict:
     """the four files of a comparison -> {file name: text}; floats as repr writes them, `matched` as 0 / 1, a missing ratio as null"""
-    return {f"{name}-pairs.csv": _csv(PAIR_COLUMNS, result["pairs"]), f"{name}-pred.csv": _csv(CELL_COLUMNS, result["pred"]),
-            f"{name}-ref.csv": _csv(CELL_COLUMNS, result["ref"]), f"{name}-summary.json": json.dumps(result["summary"]) + "\n"}
+    files = {f"{name}-pairs.csv": _csv(PAIR_COLUMNS, result["pairs"]), f"{name}-pred.csv": _csv(CELL_COLUMNS, result["pred"]),
+             f"{name}-ref.csv": _csv(CELL_COLUMNS, result["ref"]), f"{name}-summary.json": json.dumps(result["summary"]) + "\n"}
+    if "curve" in result:  # (a comparison with scores: score_curve's rows, an undefined ratio as null)
+        files[f"{name}-curve.csv"] = _curve_csv(result["curve"])
+    return files
 
 
 def write_result(result: dict, out_dir: str, name: str = "compare") -> None:
@@ -249,13 +334,26 @@ def write_result(result: dict, out_dir: str, name: str = "compare") -> None:
         os.replace(path + ".partial", path)
 
 
-def compare_cells(pred, ref, out_dir=None, name: str = "compare", min_iou: float = 0.0, engine=None) -> dict:
+def with_scores(result: dict, scores) -> dict:
+    """match_cells' dict with score_curve's on top: the entry "curve", and its three numbers in the summary"""
+    curve = score_curve(result, scores)
+    return {**result, "curve": curve["curve"], "summary": {**result["summary"], **curve["summary"]}}
+
+
+def compare_cells(pred, ref, out_dir=None, name: str = "compare", min_iou: float = 0.0, engine=None, scores=None,
+                  score_key: str = "confidence_max") -> dict:
     """pred against ref (open_labels says what either may be), cell by cell -> match_cells' dict; with out_dir the files
     <name>-pairs.csv (pred,ref,voxels,iou), <name>-pred.csv and <name>-ref.csv (id,voxels,partners,best,best_voxels,best_iou,matched)
-    and <name>-summary.json.  Both label volumes, the pair table and its outputs are in HBM at once: MemoryError otherwise."""
+    and <name>-summary.json.  Both label volumes, the pair table and its outputs are in HBM at once: MemoryError otherwise.
+    scores: one finite number per prediction cell (n_pred of them, or n_pred + 1 with a row 0), or the path of the prediction's
+    <brain>-stats.pickle, whose entry score_key is taken - the result gains "curve" and the summary average_precision, best_f1 and
+    best_f1_score (score_curve), and <name>-curve.csv (score,kept,true_pred,detected_ref,precision,recall,f1) is written beside the
+    others.  None: results and files are what they are without scores."""
     from .engine import HipEngine
 
     min_iou = _checked_min_iou(min_iou)  # (judged before anything is opened)
+    if scores is not None:
+        scores = _open_scores(scores, score_key)  # (and so are the values; the length once n_pred is known)
     own = engine is None
     eng = engine or HipEngine(0)
     try:
@@ -268,6 +366,8 @@ def compare_cells(pred, ref, out_dir=None, name: str = "compare", min_iou: float
         table = eng.cc_overlap(labels_a, n_a, labels_b, n_b)
         del labels_a, labels_b
         result = match_cells(table, counts_a, counts_b, min_iou)
+        if scores is not None:
+            result = with_scores(result, scores)
         if out_dir is not None:
             write_result(result, out_dir, name)
         return result
@@ -286,12 +386,16 @@ def main(argv=None) -> int:
     ap.add_argument("--name", default="compare")
     ap.add_argument("--min-iou", type=float, default=0.0, help="a pair hits when its IoU is at least this (default 0: any overlap)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--scores", metavar="PICKLE", default=None,
+                    help="the prediction's <brain>-stats.pickle: adds <name>-curve.csv and average_precision / best_f1 to the summary")
+    ap.add_argument("--score-key", metavar="KEY", default="confidence_max", help="the pickle's entry that scores the cells")
     args = ap.parse_args(argv)
     from .engine import HipEngine
 
     eng = HipEngine(args.device)
     try:
-        result = compare_cells(args.pred, args.ref, args.out, args.name, args.min_iou, engine=eng)
+        result = compare_cells(args.pred, args.ref, args.out, args.name, args.min_iou, engine=eng, scores=args.scores,
+                               score_key=args.score_key)
     finally:
         eng.close()
     print(json.dumps(result["summary"]), flush=True)

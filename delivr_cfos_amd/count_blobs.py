@@ -16,10 +16,11 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import hostio, label_runs
-from .hostlogic import (QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_intensity_csv_text,
-                        cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget, count_options, csv_name,
-                        finish_intensity, finish_quartiles, finish_shape, finish_shell, finish_shell_quartiles, finish_split,
-                        measuring_plan, merge_intensity, merge_shape, merge_shell)
+from .hostlogic import (QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_confidence_csv_text,
+                        cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
+                        count_options, csv_name, finish_confidence, finish_intensity, finish_quartiles, finish_shape, finish_shell,
+                        finish_shell_quartiles, finish_split, measuring_plan, merge_confidence, merge_intensity, merge_shape,
+                        merge_shell)
 
 
 def _find_cached(path: str, suffix: str, brain: str):
@@ -118,6 +119,31 @@ def _open_raw_volume(settings, brain, shape):
     return vol, path
 
 
+def _open_prob_volume(path_in, brain, shape):
+    """The probabilities of settings["mi355x"]["confidence_stats"]: <path_in>/<brain>/binary_segmentations/network_output.npy, the
+    file run_inference writes next to binaries.npy with FLAGS.SAVE_ACTIVATED_OUTPUT, as a read-only memmap -> (memmap, path).
+    FileNotFoundError without the file; ValueError unless it is a C-ordered '<f4' volume of exactly the stack's shape."""
+    path = os.path.join(path_in, brain, "binary_segmentations", "network_output.npy")
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"count_blobs: settings['mi355x']['confidence_stats'] needs the probabilities {path}: run step 2 with "
+                                "FLAGS.SAVE_ACTIVATED_OUTPUT")
+    vol = np.load(path, mmap_mode="r")
+    if vol.dtype != np.dtype("<f4") or vol.ndim != 3 or not vol.flags.c_contiguous or tuple(vol.shape) != tuple(shape):
+        raise ValueError(f"count_blobs: {path} ({vol.dtype}, shape {tuple(vol.shape)}) is not the C-ordered '<f4' volume of shape "
+                         f"{tuple(shape)} that step 2 writes with FLAGS.SAVE_ACTIVATED_OUTPUT")
+    return vol, path
+
+
+def _measure_confidence(eng, labels_dev, prob_planes, N) -> dict:
+    """prob_planes: the planes of the probability memmap that lie under labels_dev.  One upload of them, HipEngine.cc_confidence, and
+    the tensor is gone when this returns."""
+    prob_dev = hostio.upload(eng, prob_planes, what="h2d_prob")
+    try:
+        return eng.cc_confidence(labels_dev, prob_dev, N)
+    finally:
+        del prob_dev
+
+
 class _Measured(NamedTuple):
     """what _measure_raw took from the raw volume; None for what the plan did not ask for"""
     cells: Optional[dict]  # HipEngine.cc_intensity's dict of the cells - hostlogic.finish_intensity's / merge_intensity's input
@@ -205,8 +231,9 @@ def _write_table(path_out, folder, brain, text):
         fh.write(text)
 
 
-def _write_tables(path_out, brain, stats, N, opts, raw_file):
-    """the tables of the opt-in statistics `opts` asks for, and what count_blobs.last_intensity / last_quartiles / last_shape say"""
+def _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file=None):
+    """the tables of the opt-in statistics `opts` asks for, and what count_blobs.last_intensity / last_quartiles / last_shape /
+    last_confidence say"""
     def for_table(shell_keys):  # (shell entries of a cached pickle do not reach the table of a run without the key)
         return stats if opts.shell_radius else {k: v for k, v in stats.items() if k not in shell_keys}
 
@@ -221,9 +248,12 @@ def _write_tables(path_out, brain, stats, N, opts, raw_file):
     if opts.shape:
         _write_table(path_out, "cell_shape", brain, cell_shape_csv_text(stats, N))
         count_blobs.last_shape = {"n": int(N)}
+    if opts.confidence:
+        _write_table(path_out, "cell_confidence", brain, cell_confidence_csv_text(stats, N))
+        count_blobs.last_confidence = {"n": int(N), "prob_file": prob_file}
 
 
-def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts=CountOptions(), raw_vol=None):
+def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts=CountOptions(), raw_vol=None, prob_vol=None):
     """One process per GPU: every rank labels a Z-slab of the mask, seams are merged (parallel.ccl_sharded) and every
     rank writes ITS label slab straight into the output .npy (rank 0 creates the file once N - and with it the label
     dtype - is known); only the merged statistics travel to rank 0.  No rank ever holds the whole label volume (17 GB for
@@ -233,7 +263,9 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts=CountOptions(
     every rank measures planes [lo, hi) of raw_vol under its final global labels (_measure_raw_of_slab), rank 0 merges the parts
     into its stats.  Shape statistics: every rank takes one plane of the final global labels from either neighbour slab (a face
     of a voxel is exposed or not by its neighbour across the cut), measures its own planes of the extended slab with their
-    absolute z (HipEngine.cc_shape) and rank 0 adds the parts up.  Returns (N, stats | None)."""
+    absolute z (HipEngine.cc_shape) and rank 0 adds the parts up.  Confidence: every rank uploads planes [lo, hi) of prob_vol and
+    measures them under its final global labels - no neighbour planes are needed -, rank 0 merges the parts, a slab's peak made
+    global by its first plane (hostlogic.merge_confidence).  Returns (N, stats | None)."""
     from .parallel import ccl_sharded, merge_stats
 
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -295,6 +327,13 @@ def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts=CountOptions(
                 stats["shell_radius"] = int(opts.shell_radius)
 
         _on_every_slab(dist, "the intensity statistics", measure_slab, merge_measured)
+    if opts.confidence:
+        def confidence_of_slab():  # (after the raw tensor of the intensity statistics is gone: the two uploads never coexist)
+            if labels is not None:
+                return _measure_confidence(eng, labels, prob_vol[lo:hi], N), lo, Y * X
+
+        _on_every_slab(dist, "the confidence statistics", confidence_of_slab,
+                       lambda parts: stats.update(finish_confidence(merge_confidence(parts), stats["voxel_counts"], (Z, Y, X))))
     if opts.shape:
         def shape_of_slab():
             if labels is not None:
@@ -433,7 +472,23 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     name, checked against its header; the file is validated in full), not split or filtered again, and decoded into HBM only when
     something is still to be measured - with a complete pickle nothing is uploaded.  Decoded labels above the HBM budget and a mask
     that needs the slab-streamed path are refused (MemoryError), torch.distributed is refused with ValueError on every rank.
-    "dense" or absent: nothing of this happens, and a .runs file in the folder is ignored."""
+    "dense" or absent: nothing of this happens, and a .runs file in the folder is ignored.
+
+    ``settings["mi355x"]["confidence_stats"]`` true (on its own: no raw volume is opened): how sure the network was about every cell.
+    The blended probabilities step 2 writes with FLAGS.SAVE_ACTIVATED_OUTPUT - <path_in>/<brain>/binary_segmentations/network_output.npy,
+    next to binaries.npy, '<f4' of exactly the stack's shape - are uploaded once the raw tensor of the intensity statistics is gone and
+    measured under the final labels on the device (HipEngine.cc_confidence): every probability in fixed point, q = rint(clamp(p, 0, 1) *
+    2^24), NaN as 0, and per label the sum, the minimum, the maximum and the peak - the voxel of largest q, the first in raster order on
+    a tie - in integers.  The pickle gains confidence_sum (uint64, fixed point), confidence_min / _max / _mean (float64) and
+    confidence_peak (int64 (N+1, 3): z, y, x; row 0: zeros and -1), the table goes to <output_location>/cell_confidence/<brain>.csv,
+    ``count_blobs.last_confidence`` holds {"n", "prob_file"} and ``count_blobs.last_timings`` gains confidence_s.  A cell's
+    confidence_max is the ``threshold`` above which it disappears: compare_cells(scores=...) turns the column into a precision /
+    recall curve.  Cached labels - dense or decoded runs - are measured too, and a cached pickle without the keys is completed.  A
+    missing file, or one of another dtype or shape, is an error before any file is written; needs 4 more bytes of HBM per voxel; a mask
+    that needs the slab-streamed path is refused.  Under torch.distributed every rank measures the planes of its slab and rank 0
+    merges the parts.  A batch that ran step 2 with ``defer_write`` must join it (hostio.wait_deferred()) before this step, as for
+    binaries.npy: both files stream out on the same workers and appear under their names only when complete.  Off or absent: nothing
+    of this happens."""
     from .engine import shared_engine
 
     count_blobs.last_filter = None  # set by a run that filtered
@@ -441,6 +496,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
     count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
+    count_blobs.last_confidence = None  # set by a run with settings["mi355x"]["confidence_stats"]
     opts = count_options(settings, min_size, max_size)  # (a bad key raises here, before any file is touched)
     split, shell_radius = opts.split, opts.shell_radius
     if opts.bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
@@ -493,6 +549,17 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
             failed = f"rank {rank}: {exc!r}"
         if sharded:
             _raise_if_any_failed(dist, failed, "count_blobs: opening the raw volume of the intensity statistics")
+    prob_vol, prob_file = None, None
+    if opts.confidence:  # (as for the raw volume: before any file is written, and all ranks raise or none does)
+        failed = None
+        try:
+            prob_vol, prob_file = _open_prob_volume(path_in, brain, shape)
+        except (OSError, ValueError) as exc:
+            if not sharded:
+                raise
+            failed = f"rank {rank}: {exc!r}"
+        if sharded:
+            _raise_if_any_failed(dist, failed, "count_blobs: opening the probabilities of the confidence statistics")
     path_out = settings["postprocessing"]["output_location"]
     os.makedirs(path_out, exist_ok=True)  # (every rank may get here first)
     len_b = len(os.listdir(path_in))
@@ -512,7 +579,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         if branch[0][0] == "error":
             raise RuntimeError(f"count_blobs: rank 0 failed while looking for a cached labelling: {branch[0][1]}")
         if not branch[0][1]:
-            N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts, raw_vol)
+            N, stats = _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts, raw_vol, prob_vol)
             mine = None
             if rank == 0:
                 try:
@@ -520,7 +587,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
                         pickle.dump(stats, fh, protocol=pickle.HIGHEST_PROTOCOL)
                     with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
                         fh.write(cells_csv_bytes(stats, N))
-                    _write_tables(path_out, brain, stats, N, opts, raw_file)
+                    _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file)
                     end = datetime.datetime.now()
                     print(f"{end} {brain} {brain_i} / {len_b} Done ({dist.get_world_size()} ranks); Took {end - start}")
                 except Exception as exc:
@@ -539,11 +606,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     try:
         import time
 
-        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts, raw_vol)
+        N, stats, labels_written = _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts, raw_vol, prob_vol)
         t_csv = time.perf_counter()
         with open(path_out + csv_name(bin_img.shape, brain), "wb") as fh:
             fh.write(cells_csv_bytes(stats, N))  # (the text pandas writes for the reference, formatted by the library: dlv_cells_csv)
-        _write_tables(path_out, brain, stats, N, opts, raw_file)
+        _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file)
         count_blobs.last_timings["csv_s"] = time.perf_counter() - t_csv
         t_join = time.perf_counter()
         if defer_write:
@@ -563,14 +630,15 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     return N
 
 
-def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=CountOptions(), raw_vol=None):
+def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=CountOptions(), raw_vol=None, prob_vol=None):
     """The one-device path (also rank 0 of a sharded run that found a cached labelling): returns (N, stats, wait) - wait()
     returns when the label file is complete (it is written by a side thread while the statistics, the pickle and the CSV are
     made: 17 GB at the 4-7 GB/s one file takes from the kernel) and re-raises what that thread ran into.  opts: the opt-in keys
     (hostlogic.CountOptions).  A fresh labelling is split, then filtered, between dlv_ccl26_dev and the label write - the two
     scratch volumes of the split are gone before the raw volume is uploaded, so the two peaks do not add.  The labels - fresh or
-    cached - are measured after cc_stats: what hostlogic.measuring_plan finds missing, from one upload of raw_vol (_measure_raw),
-    then the shape accumulators; the pickle is written once, after the last of these."""
+    cached - are measured after cc_stats: what hostlogic.measuring_plan finds missing, from one upload of raw_vol (_measure_raw), then
+    the confidence from one upload of prob_vol (_measure_confidence: the raw tensor is gone by then), then the shape accumulators;
+    the pickle is written once, after the last of these."""
     import time
 
     bounds, split = opts.bounds, opts.split
@@ -747,12 +815,19 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             if got.shell_quartiles is not None:
                 stats.update(finish_shell_quartiles(*got.shell_quartiles, stats["shell_voxels"], stats["intensity_median"]))
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
-            if "shape" not in plan:
+            if not plan & {"confidence", "shape"}:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")
             if opts.quartiles:  # (HipEngine.cc_quantiles is synchronous: its share of the time since the last mark)
                 tm["intensity_s"] -= got.quartiles_s
                 tm["quartiles_s"] = got.quartiles_s
+        if "confidence" in plan:
+            if labels_dev is None:
+                labels_dev = cached_labels_to_device()
+            stats.update(finish_confidence(_measure_confidence(eng, labels_dev, prob_vol, N), stats["voxel_counts"], bin_img.shape))
+            if "shape" not in plan:
+                write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
+            mark("confidence")
         if "shape" in plan:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()

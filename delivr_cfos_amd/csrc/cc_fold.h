@@ -19,6 +19,7 @@ typedef unsigned int u32;
 typedef unsigned long long u64;
 typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
 typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int VPT = 8;                 // voxels per thread and sweep: two quads of one row
 constexpr u32 NO_VOXEL = 0xffffffffu;  // differs from every label 0..n (n < 2^32 - 1)
@@ -33,6 +34,8 @@ __device__ __forceinline__ void xor_add(u32& v, int o) { v += __shfl_xor(v, o, 6
 __device__ __forceinline__ void xor_add(u64& v, int o) { v += shfl_xor64(v, o); }
 __device__ __forceinline__ void xor_min(u32& v, int o) { v = min(v, __shfl_xor(v, o, 64)); }
 __device__ __forceinline__ void xor_max(u32& v, int o) { v = max(v, __shfl_xor(v, o, 64)); }
+__device__ __forceinline__ void xor_min(u64& v, int o) { v = min(v, shfl_xor64(v, o)); }
+__device__ __forceinline__ void xor_max(u64& v, int o) { v = max(v, shfl_xor64(v, o)); }
 
 __device__ __forceinline__ int row_sweeps(int X) { return (X + (int)blockDim.x * VPT - 1) / ((int)blockDim.x * VPT); }
 
@@ -77,6 +80,22 @@ __device__ __forceinline__ void load_raw_quads(const unsigned short* __restrict_
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[4 * q + j] = (xq[q] + j < X) ? (u32)row[xq[q] + j] : 0u;
+        }
+    }
+}
+
+// its twin for a row of a float volume: 16-byte loads where the row starts on a 16-byte boundary, 0.0f past the end
+template <bool NT>
+__device__ __forceinline__ void load_float_quads(const float* __restrict__ row, const u32 (&xq)[2], u32 X, float (&v)[VPT]) {
+    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        if (vec && xq[q] + 4u <= X) {
+            const f32x4_t u = load_vec<NT>(reinterpret_cast<const f32x4_t*>(row + xq[q]));
+            v[4 * q] = u.x; v[4 * q + 1] = u.y; v[4 * q + 2] = u.z; v[4 * q + 3] = u.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[4 * q + j] = (xq[q] + j < X) ? row[xq[q] + j] : 0.0f;
         }
     }
 }

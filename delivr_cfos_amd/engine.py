@@ -777,6 +777,32 @@ class HipEngine:
         self._leave()
         return out
 
+    def cc_confidence(self, labels, prob, n: int) -> dict:
+        """Per-label statistics of the network's probabilities under a label volume (dlv_cc_confidence_dev).  labels: int32
+        (uint32 payload) (Z,Y,X) in HBM; prob: float32 of the same shape in HBM, contiguous (the volume finalize leaves in its
+        prob tensor, network_output.npy).  Every probability is taken as q = rint(clamp(p, 0, 1) * 2^24) (NaN: 0).  ->
+        {"confidence_sum": uint64, "confidence_min_q", "confidence_max_q": uint32, "confidence_peak_index": uint64}, n+1 rows each;
+        the peak is the linear index in this volume of the voxel of largest q, the first in raster order on a tie.  A label without
+        a voxel - and row 0 - reads 0, 0xFFFFFFFF, 0 and 2^64 - 1."""
+        torch = self.torch
+        Z, Y, X = self._label_volume("cc_confidence", labels)
+        if not isinstance(prob, torch.Tensor) or prob.device != self.device:
+            raise ValueError(f"cc_confidence: prob: expected a torch tensor on {self.device}, got {type(prob).__name__} on "
+                             f"{getattr(prob, 'device', None)}")
+        if prob.dtype != torch.float32 or tuple(prob.shape) != (Z, Y, X) or not prob.is_contiguous():
+            raise ValueError(f"cc_confidence: prob: expected a contiguous float32 tensor of the labels' shape {(Z, Y, X)}, got "
+                             f"{prob.dtype} of shape {tuple(prob.shape)}")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"cc_confidence: n = {n}")
+        out = {"confidence_sum": np.zeros(n + 1, dtype=np.uint64), "confidence_min_q": np.zeros(n + 1, dtype=np.uint32),
+               "confidence_max_q": np.zeros(n + 1, dtype=np.uint32), "confidence_peak_index": np.zeros(n + 1, dtype=np.uint64)}
+        self._enter()
+        self._check(self.lib.dlv_cc_confidence_dev(self.ctx, C.c_void_p(labels.data_ptr()), C.c_void_p(prob.data_ptr()), Z, Y, X, n,
+                                                   *(a.ctypes.data_as(C.c_void_p) for a in out.values())))
+        self._leave()
+        return out
+
     def cc_shell(self, labels, radius: int, raw=None):
         """The background shell of every component (dlv_cc_shell_dev): the labels are expanded into the background by `radius`
         (1..16) synchronous steps of a 26-neighbourhood minimum - a voxel goes to the smallest label among the cells nearest to

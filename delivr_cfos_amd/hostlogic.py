@@ -290,6 +290,113 @@ def cell_quartiles_csv_text(stats: dict, n: int) -> str:
     return "\n".join(lines) + "\n"
 
 
+CONFIDENCE_SCALE = 1 << 24  # the fixed point of a probability: q = rint(clamp(p, 0, 1) * CONFIDENCE_SCALE)
+CONFIDENCE_RAW_KEYS = ("confidence_sum", "confidence_min_q", "confidence_max_q", "confidence_peak_index")  # what HipEngine.cc_confidence returns
+CONFIDENCE_KEYS = ("confidence_sum", "confidence_min", "confidence_max", "confidence_mean", "confidence_peak")  # finish_confidence's keys
+CONFIDENCE_ABSENT_MIN = 0xFFFFFFFF  # confidence_min_q of a label without a voxel (with sum 0, max 0 and the peak below)
+CONFIDENCE_NO_PEAK = 2**64 - 1  # confidence_peak_index of a label without a voxel
+_CONFIDENCE_RAW_DTYPES = (np.uint64, np.uint32, np.uint32, np.uint64)
+
+
+def confidence_stats_enabled(settings) -> bool:
+    """count_blobs' per-cell confidence: False when settings["mi355x"]["confidence_stats"] is absent or false, True when it is
+    true.  ValueError for anything but a bool."""
+    value = ((settings or {}).get("mi355x") or {}).get("confidence_stats")
+    if value is None or value is False:
+        return False
+    if value is not True:
+        raise ValueError(f"settings['mi355x']['confidence_stats'] = {value!r}: expected true or false")
+    return True
+
+
+def quantise_confidence(prob) -> np.ndarray:
+    """q(p) of HipEngine.cc_confidence in numpy: uint32 rint(clamp(p, 0, 1) * 2^24) of float32 probabilities, NaN as 0 (the
+    product is exact in float32, rint rounds half to even)"""
+    p = np.asarray(prob, dtype=np.float32)
+    p = np.clip(np.where(np.isnan(p), np.float32(0), p), 0, 1).astype(np.float32)
+    return np.rint(p * np.float32(CONFIDENCE_SCALE)).astype(np.uint32)
+
+
+def merge_confidence(parts) -> dict:
+    """Per-slab (HipEngine.cc_confidence dict, lo, plane) over the same labels 0..n - lo: the slab's first plane in the whole
+    volume, plane: the voxels Y * X of a plane - -> the dict of the whole volume: sums add, minima / maxima combine, a slab's peak
+    index becomes global by adding lo * plane, and of two peaks the larger q wins, the smaller global index on a tie (an absent
+    label is 0, 0xFFFFFFFF, 0, 2^64 - 1: it loses against every voxel).  None entries (empty slabs) are skipped; with nothing left,
+    or rows that disagree, ValueError."""
+    parts = [p for p in parts if p is not None]
+    if not parts:
+        raise ValueError("merge_confidence: no slab to merge")
+    rows = len(parts[0][0]["confidence_sum"])
+    if any(len(p[0][k]) != rows for p in parts for k in CONFIDENCE_RAW_KEYS):
+        raise ValueError("merge_confidence: the slabs do not cover the same labels")
+    total = np.zeros(rows, dtype=np.uint64)
+    lo_q = np.full(rows, CONFIDENCE_ABSENT_MIN, dtype=np.uint32)
+    hi_q = np.zeros(rows, dtype=np.uint32)
+    peak = np.full(rows, CONFIDENCE_NO_PEAK, dtype=np.uint64)
+    for part, lo, plane in parts:
+        s, mn, mx, idx = (np.asarray(part[k], dtype=dt) for k, dt in zip(CONFIDENCE_RAW_KEYS, _CONFIDENCE_RAW_DTYPES))
+        if int(lo) < 0 or int(plane) < 1:
+            raise ValueError(f"merge_confidence: a slab that starts at plane {lo} of planes of {plane} voxels")
+        there = idx != np.uint64(CONFIDENCE_NO_PEAK)
+        glob = np.where(there, idx + np.uint64(int(lo) * int(plane)), np.uint64(CONFIDENCE_NO_PEAK))
+        total += s
+        np.minimum(lo_q, mn, out=lo_q)
+        wins = (mx > hi_q) | ((mx == hi_q) & (glob < peak))
+        hi_q = np.where(wins, mx, hi_q)
+        peak = np.where(wins, glob, peak)
+    return {"confidence_sum": total, "confidence_min_q": lo_q, "confidence_max_q": hi_q, "confidence_peak_index": peak}
+
+
+def finish_confidence(merged: dict, voxel_counts, shape) -> dict:
+    """The whole-volume accumulators (HipEngine.cc_confidence / merge_confidence) of a volume of `shape` (Z, Y, X) -> what count_blobs
+    stores, N+1 rows each: confidence_sum uint64 (fixed point: CONFIDENCE_SCALE is 1.0), confidence_min / confidence_max float64 =
+    q / 2^24, confidence_mean float64 = sum / (count * 2^24) and confidence_peak int64 (N+1, 3), the z, y, x of the voxel of largest
+    probability, the first in raster order on a tie.  Row 0 and a label without a voxel read 0 and a peak of -1.  ValueError when a
+    label with voxels has no peak, one without voxels has one, or a peak lies outside the volume: labels and probabilities do not
+    belong together."""
+    counts = np.asarray(voxel_counts)
+    s, mn, mx, idx = (np.array(merged[k], dtype=dt) for k, dt in zip(CONFIDENCE_RAW_KEYS, _CONFIDENCE_RAW_DTYPES))
+    Z, Y, X = (int(v) for v in shape)
+    rows = len(s)
+    if len(counts) != rows or rows < 1 or any(len(a) != rows for a in (mn, mx, idx)):
+        raise ValueError(f"confidence statistics of {rows} rows beside voxel counts of {len(counts)}")
+    present = idx != np.uint64(CONFIDENCE_NO_PEAK)
+    present[0] = False  # (the background is not measured)
+    bad = np.flatnonzero(present[1:] != (counts[1:] != 0)) + 1
+    if len(bad):
+        l = int(bad[0])
+        raise ValueError(f"confidence statistics and voxel counts disagree on {len(bad)} label(s), first label {l}: "
+                         f"{int(counts[l])} voxels counted, {'a' if present[l] else 'no'} peak measured - labels and probabilities of "
+                         "different brains?")
+    if present.any() and int(idx[present].max()) >= Z * Y * X:
+        raise ValueError(f"a confidence peak at index {int(idx[present].max())} outside the volume of shape {(Z, Y, X)}")
+    scale = float(CONFIDENCE_SCALE)
+    out_sum = np.where(present, s, 0).astype(np.uint64)
+    lo = np.where(present, mn, 0).astype(np.float64) / scale
+    hi = np.where(present, mx, 0).astype(np.float64) / scale
+    mean = np.zeros(rows, dtype=np.float64)
+    np.divide(out_sum.astype(np.float64), counts.astype(np.float64) * scale, out=mean, where=present)
+    at = np.where(present, idx, 0).astype(np.int64)
+    peak = np.stack([at // (Y * X), (at // X) % Y, at % X], axis=1)
+    peak[~present] = -1
+    return {"confidence_sum": out_sum, "confidence_min": lo, "confidence_max": hi, "confidence_mean": mean, "confidence_peak": peak}
+
+
+def cell_confidence_csv_text(stats: dict, n: int) -> str:
+    """count_blobs' cell_confidence/<brain>.csv: header ``id,voxels,confidence_mean,confidence_min,confidence_max,peak_z,peak_y,
+    peak_x``, one row per label 1..N - all N, as cell_intensity_csv_text - integers written plainly, floats as repr of the float64
+    value, every line ended by a newline."""
+    n = int(n)
+    counts = np.asarray(stats["voxel_counts"])[1:n + 1].tolist()
+    floats = [np.asarray(stats[k], dtype=np.float64)[1:n + 1].tolist() for k in ("confidence_mean", "confidence_min", "confidence_max")]
+    peak = np.asarray(stats["confidence_peak"], dtype=np.int64)[1:n + 1].tolist()
+    if any(len(c) != n for c in [counts, peak] + floats):
+        raise ValueError("statistics shorter than the label count")
+    lines = ["id,voxels,confidence_mean,confidence_min,confidence_max,peak_z,peak_y,peak_x"]
+    lines.extend(f"{i},{c},{m!r},{lo!r},{hi!r},{z},{y},{x}" for i, (c, m, lo, hi, (z, y, x)) in enumerate(zip(counts, *floats, peak), 1))
+    return "\n".join(lines) + "\n"
+
+
 SPLIT_KEYS = ("split_parent", "split_siblings")  # finish_split's keys
 SPLIT_MAX_DEPTH = 16  # dlv_cc_split_dev's largest depth
 
@@ -507,6 +614,7 @@ class CountOptions:
     shape: bool = False  # shape_stats_enabled
     split: Optional[Tuple[int, int]] = None  # split_fused_settings
     label_file: str = "dense"  # label_file_format
+    confidence: bool = False  # confidence_stats_enabled
 
     @property
     def runs_file(self) -> bool:
@@ -532,8 +640,9 @@ def count_options(settings, min_size, max_size) -> CountOptions:
     quartiles = intensity_quartiles_enabled(settings)
     split = split_fused_settings(settings)
     shape = shape_stats_enabled(settings)
+    confidence = confidence_stats_enabled(settings)
     return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
-                        shape=shape, split=split, label_file=label_file_format(settings))
+                        shape=shape, split=split, label_file=label_file_format(settings), confidence=confidence)
 
 
 INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
@@ -551,7 +660,8 @@ def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
             ("shell", opts.intensity and shell, SHELL_STATS_KEYS),
             ("cell_quartiles", opts.quartiles, QUARTILE_KEYS),
             ("shell_quartiles", opts.quartiles and shell, SHELL_QUARTILE_STATS_KEYS),
-            ("shape", opts.shape, SHAPE_KEYS))
+            ("shape", opts.shape, SHAPE_KEYS),
+            ("confidence", opts.confidence, CONFIDENCE_KEYS))
 
     def complete(keys) -> bool:
         return (stats is not None and all(k in stats for k in keys)
@@ -560,8 +670,8 @@ def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
 
 
-_HBM_FRESH = ("intensity_stats", "background_shell", "intensity_quartiles", "shape_stats", "split_fused", "size_filter", "label_file")
-_HBM_CACHED = ("label_file", "shape_stats", "intensity_stats", "background_shell", "intensity_quartiles")  # (cached labels are not split or filtered)
+_HBM_FRESH = ("intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "split_fused", "size_filter", "label_file")
+_HBM_CACHED = ("label_file", "shape_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
 
 
 def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxels: int, budget: int, runs_decoded: bool = False) -> None:
@@ -580,6 +690,7 @@ def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxe
                              f"{s} more bytes per voxel in HBM beside {resident} and the raw volume", None),
         "intensity_quartiles": (bool(measured & {"cell_quartiles", "shell_quartiles"}), "", 2 + s + 2,
                                 f"up to 2 more bytes per voxel in HBM beside {resident}, the raw volume{' and the shell' if s else ''}", None),
+        "confidence_stats": ("confidence" in measured, "", 4, f"the probabilities (4 more bytes per voxel) in HBM beside {resident}", "measure"),
         "shape_stats": ("shape" in measured, "", 0, f"{resident} in HBM", "measure"),
         "split_fused": (opts.split is not None, f" = {opts.split and opts.split[0]}", 8,
                         f"8 more bytes per voxel in HBM beside {resident}", "split"),

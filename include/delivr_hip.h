@@ -310,6 +310,19 @@ int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, ui
 int dlv_cc_intensity_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* raw_dev, int Z, int Y, int X,
                          int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n,
                          uint64_t* sum, uint64_t* sumsq, uint16_t* vmin, uint16_t* vmax);
+/* Per-label confidence: statistics of the network's blended probabilities under a label volume (no counterpart in the reference,
+ * whose users take them on the host). prob_dev: float32 (Z,Y,X) contiguous and unpadded, like labels_dev (uint32, labels 0..n) - the
+ * volume dlv_finalize_dev leaves in prob_dev and run_inference writes as binary_segmentations/network_output.npy with
+ * FLAGS.SAVE_ACTIVATED_OUTPUT (the reference: inference/inference.py:312-318). Every probability p is taken in fixed point,
+ * q(p) = (uint32) rint(clamp(p, 0, 1) * 2^24): NaN counts as 0, +inf as 1, -inf as 0, the product is exact in float32 and rint rounds
+ * half to even; for p >= 0.5 q loses nothing. Host outputs of n+1 rows, over the voxels that hold the label: sum_q uint64, min_q and
+ * max_q uint32, peak_index uint64 = the linear index (z*Y + y)*X + x, inside the volume handed in, of the voxel of largest q, the first
+ * in C-raster order on a tie. A label with no voxel in this volume, and row 0 (the background is not measured): 0, 0xFFFFFFFF, 0 and
+ * 2^64 - 1 - so two slabs merge with +, min, max and "larger q, then smaller global index". Labels above n are not accumulated. Integer
+ * work only after q: exact and independent of scheduling. A NULL pointer, Z/Y/X < 1, Z*Y*X >= 2^39 (the peak's index has 39 bits),
+ * n >= 2^32 - 1 or a pointer not 4-byte aligned: DLV_EINVAL before any launch. Synchronous. */
+int dlv_cc_confidence_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const float* prob_dev, int Z, int Y, int X, uint64_t n,
+                          uint64_t* sum_q, uint32_t* min_q, uint32_t* max_q, uint64_t* peak_index);
 /* Per-label order statistics of a raw uint16 volume under a label volume (no counterpart in the reference). For a label l with
  * m >= 1 voxels whose raw values sorted ascending are v[0] <= ... <= v[m-1], and a level p in per cent: Q_p(l) = v[(p * (m - 1)) / 100]
  * (integer division) - the "lower" quantile, always a value the label holds; p = 50 is the lower median, p = 0 / 100 the minimum /

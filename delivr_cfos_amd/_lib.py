@@ -243,6 +243,8 @@ SIGNATURES = {
     "dlv_cc_runs_count_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_uint64)]),
     "dlv_cc_runs_emit_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "dlv_cc_runs_decode_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, _P, _P, C.c_uint64, _P]),
+    "dlv_fill_holes_u8_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint8, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dlv_cc_count_marked_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint8, _P]),
     "dlv_cc_overlap_count_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dlv_cc_overlap_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P, _P,
                                      C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -16,8 +16,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import hostio, label_runs
-from .hostlogic import (QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_confidence_csv_text,
-                        cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
+from .hostlogic import (FILL_VALUE, QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_confidence_csv_text,
+                        cell_holes_csv_text, cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
                         count_options, csv_name, finish_confidence, finish_intensity, finish_quartiles, finish_shape, finish_shell,
                         finish_shell_quartiles, finish_split, measuring_plan, merge_confidence, merge_intensity, merge_shape,
                         merge_shell)
@@ -98,6 +98,12 @@ def _note_split(split, n_before: int, n_after: int, components_split: int):
                               "components_split": int(components_split)}
     print(f"split of fused cells (depth {split[0]}, min_core {split[1]}): {components_split} of {n_before} components split, "
           f"{n_after} cells")
+
+
+def _note_fill(voxels_filled: int, holes: int, n_after: int):
+    # (the components before the fill are not named: the cells a cavity swallowed are only known from a second labelling)
+    count_blobs.last_fill = {"holes": int(holes), "voxels_filled": int(voxels_filled), "n_after": int(n_after)}
+    print(f"fill of holes: {holes} holes filled, {voxels_filled} voxels added, {n_after} components after the fill")
 
 
 def _open_raw_volume(settings, brain, shape):
@@ -251,6 +257,8 @@ def _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file=None):
     if opts.confidence:
         _write_table(path_out, "cell_confidence", brain, cell_confidence_csv_text(stats, N))
         count_blobs.last_confidence = {"n": int(N), "prob_file": prob_file}
+    if opts.fill_holes and "hole_voxels" in stats:  # (a cached labelling is not filled: its pickle may lack the key)
+        _write_table(path_out, "cell_holes", brain, cell_holes_csv_text(stats, N))
 
 
 def _count_blobs_sharded(eng, bin_img, dist, path_out, brain, opts=CountOptions(), raw_vol=None, prob_vol=None):
@@ -488,7 +496,22 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     that needs the slab-streamed path is refused.  Under torch.distributed every rank measures the planes of its slab and rank 0
     merges the parts.  A batch that ran step 2 with ``defer_write`` must join it (hostio.wait_deferred()) before this step, as for
     binaries.npy: both files stream out on the same workers and appear under their names only when complete.  Off or absent: nothing
-    of this happens."""
+    of this happens.
+
+    ``settings["mi355x"]["fill_holes"]`` true: the holes of the mask are filled on the device between the upload and the labelling
+    (HipEngine.fill_holes).  A hole is a 6-connected background component that reaches no face of the volume - exactly
+    scipy.ndimage.binary_fill_holes(mask != 0): background that leaves a cavity only over an edge or a corner is sealed in, a cavity
+    open to a face of the volume stays, and a cell inside the cavity of another is swallowed by it.  The order is fill, label, split,
+    size filter, measure, write: everything written - label file (dense or runs), its name, statistics, CSV (``Size`` is the filled
+    size), tables - is what the filled mask gives.  The mask stays in HBM, 1 byte per voxel, until the filled voxels have been counted
+    under the final labels (HipEngine.cc_count_marked); the pickle gains hole_voxels (uint32, N+1 rows, row 0 zero: the voxels the fill
+    added to each final cell) and holes_filled (the holes of the whole mask), the table goes to <output_location>/cell_holes/<brain>.csv,
+    ``count_blobs.last_fill`` holds {"holes", "voxels_filled", "n_after"} and ``count_blobs.last_timings`` gains fill_holes_s and
+    hole_voxels_s.  binaries.npy is step 2's file and is NOT rewritten: blob_highlighter's default box path multiplies by it and
+    leaves the cavities unpainted, "paint_from": "labels" paints them.  A cached labelling - dense or runs - is reused as it is: it is
+    NOT filled.  A mask that needs the slab-streamed path is refused (MemoryError), torch.distributed is refused with ValueError on
+    every rank: a cavity that crosses a slab cut is closed on neither side.  Off or absent: nothing of this happens, and no new kernel
+    is launched."""
     from .engine import shared_engine
 
     count_blobs.last_filter = None  # set by a run that filtered
@@ -497,6 +520,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
     count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
     count_blobs.last_confidence = None  # set by a run with settings["mi355x"]["confidence_stats"]
+    count_blobs.last_fill = None  # set by a run that filled holes (settings["mi355x"]["fill_holes"])
     opts = count_options(settings, min_size, max_size)  # (a bad key raises here, before any file is touched)
     split, shell_radius = opts.split, opts.shell_radius
     if opts.bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
@@ -516,6 +540,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['split_fused'] = {split[0]} is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
                          "its own; run step 3 on one device or switch split_fused off")
+    if sharded and opts.fill_holes:
+        # (as for split_fused: all raise, before any collective, or none does)
+        raise ValueError(f"count_blobs: settings['mi355x']['fill_holes'] is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): a cavity that crosses a slab cut is closed on neither side, so a Z-slab cannot "
+                         "be filled on its own; run step 3 on one device or switch fill_holes off")
     if sharded and opts.runs_file:
         # (as for split_fused: all raise, before any collective, or none does)
         raise ValueError(f"count_blobs: settings['mi355x']['label_file'] = \"runs\" is not available under torch.distributed "
@@ -695,9 +724,16 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             # readers / writers (hostio.py): 4.3 GB in and 17 GB out for a 1024 x 2048 x 2048 brain, around 20 ms of kernels
             mask_dev = hostio.upload(eng, bin_img, what="h2d_mask")
             mark("upload")
+            filled = None
+            if opts.fill_holes:
+                filled = eng.fill_holes(mask_dev, FILL_VALUE)
+                mark("fill_holes")
             labels_dev, N = eng.ccl26(mask_dev)
-            del mask_dev
+            if filled is None:
+                del mask_dev
             mark("ccl26")
+            if filled is not None:
+                _note_fill(filled[0], filled[1], N)
             split_parent = None
             if split is not None:
                 n_components = N
@@ -714,6 +750,12 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                     split_parent = np.concatenate([split_parent[:1], split_parent[1:][_keep_mask(counts, bounds)[1:]]])
                 del counts_dev
                 mark("size_filter")
+            hole_voxels = None
+            if filled is not None:  # (under the final labels; the filled voxels of the cells the filter removed carry label 0)
+                hole_voxels = eng.cc_count_marked(labels_dev, mask_dev, N, FILL_VALUE).cpu().numpy().view(np.uint32).copy()
+                hole_voxels[0] = 0
+                del mask_dev
+                mark("hole_voxels")
             from concurrent.futures import ThreadPoolExecutor
 
             writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dlv-labels")
@@ -754,7 +796,9 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                 print(f"size filter: the cached labelling is reused as it is, min_size {bounds[0]} / max_size {bounds[1]} are not applied to it")
             if split is not None:
                 print(f"split of fused cells: the cached labelling is reused as it is, it is not split (depth {split[0]}) again")
-            split_parent = None
+            if opts.fill_holes:
+                print("fill of holes: the cached labelling is reused as it is, its holes are not filled")
+            split_parent, hole_voxels, filled = None, None, None
             labels = None if runs is not None else np.load(cached, mmap_mode="r")
         mid = datetime.datetime.now()
         print(f"{mid} labelling+writing/loading took {mid - start} : {N}")
@@ -798,9 +842,14 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             if split_parent is not None:
                 stats.update(finish_split(split_parent, count_blobs.last_split["n_before"]))
                 stats["split_depth"] = int(split[0])
+            if hole_voxels is not None:
+                stats["hole_voxels"], stats["holes_filled"] = hole_voxels, int(filled[1])
             if not plan:
                 write_stats(os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("stats")
+        elif hole_voxels is not None:  # (a pickle found beside a fresh labelling is completed, as for the measured keys)
+            stats["hole_voxels"], stats["holes_filled"] = hole_voxels, int(filled[1])
+            write_stats(cached_stats)
         if plan & RAW_GROUPS:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()

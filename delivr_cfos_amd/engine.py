@@ -611,6 +611,55 @@ class HipEngine:
         self._leave()
         return labels, int(n.value)
 
+    def _byte_volume(self, what: str, mask):
+        """the tensor checks of a uint8 (Z,Y,X) mask in HBM -> (Z, Y, X)"""
+        torch = self.torch
+        if not isinstance(mask, torch.Tensor) or mask.device != self.device:
+            raise ValueError(f"{what}: mask: expected a torch tensor on {self.device}, got {type(mask).__name__} on "
+                             f"{getattr(mask, 'device', None)}")
+        if mask.dtype != torch.uint8 or mask.dim() != 3 or not mask.is_contiguous() or mask.numel() == 0:
+            raise ValueError(f"{what}: mask: expected a contiguous, non-empty 3-D uint8 tensor, got {mask.dtype} of shape "
+                             f"{tuple(mask.shape)}")
+        return tuple(int(v) for v in mask.shape)
+
+    def fill_holes(self, mask, fill_value: int = 2):
+        """Exact hole filling of a uint8 (Z,Y,X) mask in HBM, in place (dlv_fill_holes_u8_dev): every voxel of every background
+        component that reaches no face of the volume (6-connected; scipy.ndimage.binary_fill_holes(mask != 0)) becomes fill_value,
+        no other byte is written.  The mask must not hold fill_value already.  -> (voxels_filled, holes)."""
+        Z, Y, X = self._byte_volume("fill_holes", mask)
+        if isinstance(fill_value, bool) or not isinstance(fill_value, (int, np.integer)) or not 1 <= int(fill_value) <= 255:
+            raise ValueError(f"fill_holes: fill_value = {fill_value!r}: expected an integer 1..255")
+        voxels, holes = C.c_uint64(), C.c_uint64()
+        self._enter()
+        try:
+            self._check(self.lib.dlv_fill_holes_u8_dev(self.ctx, C.c_void_p(mask.data_ptr()), Z, Y, X, int(fill_value), C.byref(voxels),
+                                                       C.byref(holes)))
+        finally:
+            self._leave()
+        return int(voxels.value), int(holes.value)
+
+    def cc_count_marked(self, labels, mask, n: int, value: int):
+        """Per label 0..n the voxels whose mask byte equals `value` (dlv_cc_count_marked_dev): on the labels of a filled mask, the
+        voxels fill_holes gave each component.  labels: int32 (uint32 payload) (Z,Y,X) in HBM, mask: uint8 of the same shape.
+        -> int32 tensor (uint32 payload) of n+1 in HBM, like cc_counts."""
+        torch = self.torch
+        shape = self._label_volume("cc_count_marked", labels)
+        if self._byte_volume("cc_count_marked", mask) != shape:
+            raise ValueError(f"cc_count_marked: mask of shape {tuple(mask.shape)}, the labels are {shape}")
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= 255:
+            raise ValueError(f"cc_count_marked: value = {value!r}: expected an integer 0..255")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"cc_count_marked: n = {n}")
+        counts = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+        self._enter()
+        try:
+            self._check(self.lib.dlv_cc_count_marked_dev(self.ctx, C.c_void_p(labels.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                         int(labels.numel()), n, int(value), C.c_void_p(counts.data_ptr())))
+        finally:
+            self._leave()
+        return counts
+
     def ccl_ran(self) -> dict:
         """what the last dlv_ccl26_dev of this context launched (include/delivr_hip_diag.h: dlv_ccl_ran) - tests"""
         out = _lib.CclRan()

@@ -588,6 +588,33 @@ def cell_shape_csv_text(stats: dict, n: int) -> str:
     return "\n".join(lines) + "\n"
 
 
+def fill_holes_enabled(settings) -> bool:
+    """count_blobs' hole filling of the cell mask: False when settings["mi355x"]["fill_holes"] is absent or false, True when it is
+    true.  ValueError for anything but a bool."""
+    value = ((settings or {}).get("mi355x") or {}).get("fill_holes")
+    if value is None or value is False:
+        return False
+    if value is not True:
+        raise ValueError(f"settings['mi355x']['fill_holes'] = {value!r}: expected true or false")
+    return True
+
+
+HOLE_KEYS = ("hole_voxels", "holes_filled")  # what settings["mi355x"]["fill_holes"] adds to the statistics
+FILL_VALUE = 2  # the byte count_blobs' fill writes into the mask in HBM: binaries.npy holds 0 and 1
+
+
+def cell_holes_csv_text(stats: dict, n: int) -> str:
+    """The table of settings["mi355x"]["fill_holes"], one row per label 1..n: the cell's size after the fill and the voxels the
+    fill added to it."""
+    n = int(n)
+    cols = [np.asarray(stats[k])[1:n + 1].tolist() for k in ("voxel_counts", "hole_voxels")]
+    if any(len(c) != n for c in cols):
+        raise ValueError("statistics shorter than the label count")
+    lines = ["Blob,Size,HoleVoxels"]
+    lines.extend(f"{i},{c},{h}" for i, (c, h) in enumerate(zip(*cols), 1))
+    return "\n".join(lines) + "\n"
+
+
 LABEL_FILE_FORMATS = ("dense", "runs")
 
 
@@ -615,6 +642,7 @@ class CountOptions:
     split: Optional[Tuple[int, int]] = None  # split_fused_settings
     label_file: str = "dense"  # label_file_format
     confidence: bool = False  # confidence_stats_enabled
+    fill_holes: bool = False  # fill_holes_enabled
 
     @property
     def runs_file(self) -> bool:
@@ -641,8 +669,10 @@ def count_options(settings, min_size, max_size) -> CountOptions:
     split = split_fused_settings(settings)
     shape = shape_stats_enabled(settings)
     confidence = confidence_stats_enabled(settings)
+    fill = fill_holes_enabled(settings)
     return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
-                        shape=shape, split=split, label_file=label_file_format(settings), confidence=confidence)
+                        shape=shape, split=split, label_file=label_file_format(settings), confidence=confidence,
+                        fill_holes=fill)
 
 
 INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
@@ -670,7 +700,7 @@ def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
 
 
-_HBM_FRESH = ("intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "split_fused", "size_filter", "label_file")
+_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "split_fused", "size_filter", "label_file")
 _HBM_CACHED = ("label_file", "shape_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
 
 
@@ -685,6 +715,9 @@ def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxe
     raw = bool(RAW_GROUPS & measured)
     s = opts.shell_bytes_per_voxel
     rows = {  # key: (it applies, its value in the settings, bytes per voxel beside the resident ones, what it needs, what streaming lacks)
+        # (the mask, 1 of the resident bytes, stays until the filled voxels are counted under the final labels: through the split
+        # and the filter; the gap table of the fill - 8 bytes per row, 10 per gap - is made before the labels exist)
+        "fill_holes": (opts.fill_holes, "", 0, f"{resident} and the gap table in HBM", "fill holes"),
         "intensity_stats": (raw, "", 2, f"the raw volume in HBM beside {resident}", "measure"),
         "background_shell": ("shell" in measured, f" = {opts.shell_radius}", 2 + s,
                              f"{s} more bytes per voxel in HBM beside {resident} and the raw volume", None),

@@ -399,6 +399,27 @@ int dlv_cc_runs_emit_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y,
                          uint16_t* x0_dev, uint16_t* x1_dev, uint32_t* label_dev);
 int dlv_cc_runs_decode_dev(dlv_ctx* ctx, const uint64_t* row_start_dev, uint64_t n_rows, int X, const uint16_t* x0_dev,
                            const uint16_t* x1_dev, const uint32_t* label_dev, uint64_t n_runs, uint32_t* labels_out_dev);
+/* Exact hole filling of a byte mask, in place (no counterpart in the reference, whose users call scipy.ndimage.binary_fill_holes
+ * on the host; csrc/fill_holes.hip). mask_dev: uint8 (Z,Y,X) contiguous; the foreground is every voxel that is not 0. Two background
+ * voxels are connected when they share a face (6-connectivity); the voxels outside the volume count as background and are all
+ * connected to each other. A hole is a background component with no voxel on any of the six faces of the volume: every voxel of
+ * every hole is written as fill_value, and no other byte of the mask is written. This is binary_fill_holes(mask != 0) with its default
+ * structure. Background that reaches the rest only over an edge or a corner is sealed; a cavity open to a face of the volume is not
+ * a hole; a component inside the cavity of another is swallowed by it; a hole never holds the first voxel of the component around
+ * it, so dlv_ccl26_dev on the filled mask numbers the surviving components in the order they had.
+ * *voxels_filled = the hole voxels, *holes = the holes (the background components filled). Integer work only: exact and independent
+ * of scheduling. DLV_EINVAL with the mask untouched for a NULL pointer, Z/Y/X < 1, fill_value == 0, or a mask that already holds
+ * fill_value somewhere (the caller tells filled voxels from original ones by it); DLV_EUNSUP with the mask untouched for X > 65536
+ * and for more than 2^32 voxels (as the run coder and dlv_ccl26_dev). Device scratch: 8 bytes per row and 10 bytes per gap (a
+ * background stretch of a row with foreground on both sides), in the context's slots. Synchronous.
+ *  dlv_cc_count_marked_dev: counts_dev[l] = the voxels with label l whose mask byte equals value, for l = 0..n (device array of n+1
+ *    uint32; labels_dev: nvox uint32, 4-byte aligned; mask_dev: nvox bytes; labels above n are not counted, as in
+ *    dlv_cc_counts_dev). On the labels of a filled mask with value = fill_value: the voxels the fill gave each component.
+ *    n >= 2^32 - 1, a NULL or a misaligned pointer: DLV_EINVAL. Asynchronous on the context's stream. */
+int dlv_fill_holes_u8_dev(dlv_ctx* ctx, uint8_t* mask_dev, int Z, int Y, int X, uint8_t fill_value, uint64_t* voxels_filled,
+                          uint64_t* holes);
+int dlv_cc_count_marked_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint8_t* mask_dev, uint64_t nvox, uint64_t n, uint8_t value,
+                            uint32_t* counts_dev);
 /* The overlap table of two label volumes (no counterpart in the reference; csrc/cc_overlap.hip, delivr_cfos_amd/compare_cells.py): every
  * pair of labels (a, b) that share voxels, with the number of voxels they share. a_dev, b_dev: uint32 (Z,Y,X) contiguous, 4-byte
  * aligned, labels below 2^32 - 1. A voxel takes part when 1 <= a <= n_a and 1 <= b <= n_b: the background and labels above n in either

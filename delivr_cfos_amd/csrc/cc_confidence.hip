@@ -11,6 +11,7 @@
 // (q << 39) | (2^39 - 1 - index): the larger q wins, then the smaller index.  A volume of fewer than 2^39 voxels keeps the
 // index inside its 39 bits and the key of every voxel above 0, the value of a label without a voxel.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
 
 #include <algorithm>
@@ -91,11 +92,11 @@ __global__ void __launch_bounds__(256) cc_confidence_kernel(const u32* __restric
 extern "C" int dlv_cc_confidence_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const float* prob_dev, int Z, int Y, int X, uint64_t n,
                                      uint64_t* sum_q, uint32_t* min_q, uint32_t* max_q, uint64_t* peak_index) {
     if (!ctx || !labels_dev || !prob_dev || !sum_q || !min_q || !max_q || !peak_index) return DLV_EINVAL;
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_confidence: empty volume");
+    DLV_TRY(check_volume(ctx, "cc_confidence", Z, Y, X));
     if ((u64)Z * Y > INDEX_MASK / (u64)X)  // (Z * Y fits 62 bits; the product of all three could wrap)
         return dlv_fail(ctx, DLV_EINVAL, "cc_confidence: a volume of %d x %d x %d voxels: the peak's index has %d bits", Z, Y, X, INDEX_BITS);
     const u64 nvox = (u64)Z * Y * X;
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_confidence: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_label_count(ctx, "cc_confidence", n));
     if (((uintptr_t)labels_dev & 3) || ((uintptr_t)prob_dev & 3))
         return dlv_fail(ctx, DLV_EINVAL, "cc_confidence: labels and probabilities must be 4-byte aligned");
     DLV_HIP(ctx, hipSetDevice(ctx->device));

@@ -13,13 +13,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace {
+#include "cc_types.h"
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
-typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
+namespace {
 
 constexpr int VPT = 8;                 // voxels per thread and sweep: two quads of one row
 constexpr u32 NO_VOXEL = 0xffffffffu;  // differs from every label 0..n (n < 2^32 - 1)

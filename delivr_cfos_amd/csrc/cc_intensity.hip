@@ -6,6 +6,7 @@
 // Integer work only (u64 sums, u32 minima / maxima): results are exact and independent of scheduling.  No overflow: a
 // component has at most 2^32 - 1 voxels and 65535^2 < 2^32, so the sum of squares stays below 2^64.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
 
 #include <algorithm>
@@ -80,11 +81,9 @@ extern "C" int dlv_cc_intensity_dev(dlv_ctx* ctx, const uint32_t* labels_dev, co
                                     int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n, uint64_t* sum, uint64_t* sumsq,
                                     uint16_t* vmin, uint16_t* vmax) {
     if (!ctx || !labels_dev || !raw_dev || !sum || !sumsq || !vmin || !vmax) return DLV_EINVAL;
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_intensity: empty volume");
-    if (raw_pitch_y < X || raw_pitch_z / Y < raw_pitch_y)
-        return dlv_fail(ctx, DLV_EINVAL, "cc_intensity: raw pitches (%lld, %lld) do not hold rows of %d and planes of %d rows",
-                        (long long)raw_pitch_z, (long long)raw_pitch_y, X, Y);
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_intensity: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_volume(ctx, "cc_intensity", Z, Y, X));
+    DLV_TRY(check_raw_pitches(ctx, "cc_intensity", Y, X, raw_pitch_y, raw_pitch_z));
+    DLV_TRY(check_label_count(ctx, "cc_intensity", n));
     if (((uintptr_t)labels_dev & 3) || ((uintptr_t)raw_dev & 1))
         return dlv_fail(ctx, DLV_EINVAL, "cc_intensity: labels must be 4-byte aligned, raw 2-byte aligned");
     DLV_HIP(ctx, hipSetDevice(ctx->device));

@@ -37,6 +37,7 @@
 // voxel (2.88 million segments, 538 627 pairs, 2^23 slots = 128 MiB): 5.57 / 5.55 / 0.21 ms beside 5.01 ms - count and insert read
 // their 8 bytes per voxel at 6.2 TB/s, 1.11 of a cc_stats pass each, against the bound of two.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
 
 #include <algorithm>
@@ -265,7 +266,7 @@ __global__ void __launch_bounds__(CT) cc_overlap_compact_kernel(const u64* __res
 
 // what both entries check of the volumes, before anything is launched
 int overlap_args(dlv_ctx* ctx, const char* what, const void* a_dev, const void* b_dev, int Z, int Y, int X, uint64_t n_a, uint64_t n_b) {
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "%s: empty volume", what);
+    DLV_TRY(check_volume(ctx, what, Z, Y, X));
     if (X > MAX_X) return dlv_fail(ctx, DLV_EUNSUP, "%s: X = %d exceeds %d", what, X, MAX_X);
     if (n_a > 0xfffffffeull || n_b > 0xfffffffeull)
         return dlv_fail(ctx, DLV_EINVAL, "%s: n_a = %llu, n_b = %llu do not fit the uint32 labels", what, (unsigned long long)n_a,

@@ -23,6 +23,7 @@
 // Integer work only: the result is exact and independent of scheduling.  After the gather a label's cursor is its segment's
 // end, which is the start of the next label's segment: the selection needs no second table.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
 
 #include <algorithm>
@@ -199,11 +200,9 @@ extern "C" int dlv_cc_quantiles_dev(dlv_ctx* ctx, const uint32_t* labels_dev, co
                                     int64_t raw_pitch_y, int64_t raw_pitch_z, uint64_t n, int n_levels, const int* levels,
                                     uint16_t* out, uint32_t* counts) {
     if (!ctx || !labels_dev || !raw_dev || !levels || !out || !counts) return DLV_EINVAL;
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_quantiles: empty volume");
-    if (raw_pitch_y < X || raw_pitch_z / Y < raw_pitch_y)
-        return dlv_fail(ctx, DLV_EINVAL, "cc_quantiles: raw pitches (%lld, %lld) do not hold rows of %d and planes of %d rows",
-                        (long long)raw_pitch_z, (long long)raw_pitch_y, X, Y);
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_quantiles: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_volume(ctx, "cc_quantiles", Z, Y, X));
+    DLV_TRY(check_raw_pitches(ctx, "cc_quantiles", Y, X, raw_pitch_y, raw_pitch_z));
+    DLV_TRY(check_label_count(ctx, "cc_quantiles", n));
     if (((uintptr_t)labels_dev & 3) || ((uintptr_t)raw_dev & 1))
         return dlv_fail(ctx, DLV_EINVAL, "cc_quantiles: labels must be 4-byte aligned, raw 2-byte aligned");
     if (n_levels < 1 || n_levels > MAX_LEVELS) return dlv_fail(ctx, DLV_EINVAL, "cc_quantiles: %d levels, expected 1..%d", n_levels, MAX_LEVELS);

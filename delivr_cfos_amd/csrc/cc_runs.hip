@@ -21,7 +21,9 @@
 // cells (671 008 runs; 0.069 of cc_stats_kernel on the same labels, against the bound of 2) and 0.355 ms on a 50 % random mask
 // (33.6 million runs); the decode 0.313 and 0.603 ms.  1024 x 2048 x 2048, the bench's cell mask: 7 ms with the download of the runs.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
+#include "dev_scan.h"
 
 #include <algorithm>
 
@@ -29,7 +31,6 @@ namespace {
 
 constexpr int RT = 64;                 // threads per workgroup: one wave, one row at a time
 constexpr u64 RUNS_MAX_WG = 256 * 32;  // workgroups per launch; rows beyond that are walked grid-stride
-constexpr int RGRP = 1024;             // rows per scan group
 
 // The labels of this lane's two quads of sweep sw and the voxel before / after each quad (NO_VOXEL outside the row: it differs
 // from every label, so a row's first voxel starts a run and its last one ends one).  The neighbours come from the lanes next to
@@ -85,82 +86,6 @@ __global__ void __launch_bounds__(RT) cc_runs_count_kernel(const u32* __restrict
         }
         for (int o = 32; o > 0; o >>= 1) xor_add(c, o);
         if ((threadIdx.x & 63) == 0) counts[r] = c;
-    }
-}
-
-// ---- exclusive scan of the row counts into the 64-bit row_start: 32-bit sums inside groups of 1024 rows (<= 2^26 runs) under
-// 64-bit group sums - ccl.hip's three coalesced steps, with nothing above a group in 32 bits ------------------------------------
-__device__ __forceinline__ u32 block_excl_scan_256(u32 v, u32* total) {
-    __shared__ u32 wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    u32 base = 0;
-    for (int k = 0; k < wave; ++k) base += wsum[k];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return base + incl - v;
-}
-
-__global__ void __launch_bounds__(256) cc_runs_scan_sums_kernel(const u32* __restrict__ counts, u64 nrows, u64* __restrict__ gsum) {
-    const u64 g0 = (u64)blockIdx.x * RGRP;
-    u32 s = 0;
-    for (int i = threadIdx.x; i < RGRP; i += 256)
-        if (g0 + i < nrows) s += counts[g0 + i];
-    u32 total;
-    block_excl_scan_256(s, &total);
-    if (threadIdx.x == 0) gsum[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(1024) cc_runs_scan_groups_kernel(u64* __restrict__ gsum, u64 ng, u64* __restrict__ total_out) {
-    __shared__ u64 part[1024];
-    const u64 per = (ng + 1023) / 1024;
-    const u64 b0 = min((u64)threadIdx.x * per, ng), b1 = min(b0 + per, ng);
-    u64 s = 0;
-    for (u64 i = b0; i < b1; ++i) s += gsum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 run = 0;
-        for (int k = 0; k < 1024; ++k) {
-            const u64 v = part[k];
-            part[k] = run;
-            run += v;
-        }
-        *total_out = run;  // row_start[nrows] = R (<= the voxels of the volume)
-    }
-    __syncthreads();
-    u64 run = part[threadIdx.x];
-    for (u64 i = b0; i < b1; ++i) {
-        const u64 v = gsum[i];
-        gsum[i] = run;
-        run += v;
-    }
-}
-
-__global__ void __launch_bounds__(256) cc_runs_scan_apply_kernel(const u32* __restrict__ counts, u64 nrows, const u64* __restrict__ gsum,
-                                                                 u64* __restrict__ row_start) {
-    const u64 g0 = (u64)blockIdx.x * RGRP;
-    u32 v[RGRP / 256];
-    u32 mine = 0;
-#pragma unroll
-    for (int k = 0; k < RGRP / 256; ++k) {  // thread t owns the 4 consecutive rows 4t .. 4t+3 of the group
-        const u64 i = g0 + (u64)threadIdx.x * (RGRP / 256) + k;
-        v[k] = i < nrows ? counts[i] : 0u;
-        mine += v[k];
-    }
-    u32 total;
-    u64 run = gsum[blockIdx.x] + block_excl_scan_256(mine, &total);
-#pragma unroll
-    for (int k = 0; k < RGRP / 256; ++k) {
-        const u64 i = g0 + (u64)threadIdx.x * (RGRP / 256) + k;
-        if (i < nrows) row_start[i] = run;
-        run += v[k];
     }
 }
 
@@ -261,7 +186,7 @@ __global__ void __launch_bounds__(RT) cc_runs_decode_kernel(const u64* __restric
 }
 
 int runs_geometry(dlv_ctx* ctx, const char* what, int Z, int Y, int X) {
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "%s: empty volume", what);
+    DLV_TRY(check_volume(ctx, what, Z, Y, X));
     if (X > 65536) return dlv_fail(ctx, DLV_EUNSUP, "%s: X = %d, x0 / x1 are uint16", what, X);
     return DLV_OK;
 }
@@ -279,7 +204,7 @@ int dlv_cc_runs_count_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y
         return dlv_fail(ctx, DLV_EINVAL, "cc_runs_count: labels must be 4-byte, row_start 8-byte aligned");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     const u64 nrows = (u64)Z * Y;
-    const u64 ng = (nrows + RGRP - 1) / RGRP;  // (one workgroup per group in the scan)
+    const u64 ng = scan_groups(nrows);  // (one workgroup per group in the scan)
     if (ng > 0x7fffffffull) return dlv_fail(ctx, DLV_EUNSUP, "cc_runs_count: %llu rows exceed the launch grid", (unsigned long long)nrows);
     // [counts u32 nrows | pad | group sums u64 ng]
     const size_t off_gsum = ((size_t)nrows * 4 + 7) & ~(size_t)7;
@@ -289,11 +214,10 @@ int dlv_cc_runs_count_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y
     u64* gsum = (u64*)(ws + off_gsum);
     DlvProf pr(ctx, "cc_runs_count", 0.0, (double)nrows * X * 4);
     hipLaunchKernelGGL(cc_runs_count_kernel, dim3(runs_grid(nrows)), dim3(RT), 0, ctx->stream, labels_dev, nrows, X, counts);
-    hipLaunchKernelGGL(cc_runs_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, counts, nrows, gsum);
-    hipLaunchKernelGGL(cc_runs_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, gsum, ng, (u64*)row_start_dev + nrows);
-    hipLaunchKernelGGL(cc_runs_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, counts, nrows, gsum, (u64*)row_start_dev);
+    // the counts into the 64-bit row_start: 32-bit sums inside a scan group of 1024 rows (<= 2^26 runs), nothing above a group in
+    // 32 bits; row_start[nrows] = R (<= the voxels of the volume)
+    DLV_TRY(dev_excl_scan(ctx, counts, nrows, (u64*)row_start_dev, gsum, (u64*)row_start_dev + nrows, "cc_runs_count_kernel"));
     pr.end();
-    DLV_LAUNCH_CHECK(ctx, "cc_runs_count_kernel");
     DLV_HIP(ctx, hipMemcpyAsync(n_runs, row_start_dev + nrows, 8, hipMemcpyDeviceToHost, ctx->stream));
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DLV_OK;

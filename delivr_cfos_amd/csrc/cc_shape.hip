@@ -11,6 +11,7 @@
 // Measured once on an MI355X (profiles/README.md, "cc_shape"): 512^3 labels, 1.48 ms on a 1 % mask of small cells and 37.8 ms on a
 // 50 % random mask (one giant component: bound by the atomics on its row), 0.46 and 0.78 of cc_stats_kernel on the same labels.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
 
 #include <algorithm>
@@ -131,11 +132,11 @@ extern "C" int dlv_cc_shape_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Zb
                                 uint64_t n, uint32_t* counts, uint64_t* sums, uint64_t* moments, uint64_t* faces,
                                 uint32_t* surface_voxels) {
     if (!ctx || !labels_dev || !counts || !sums || !moments || !faces || !surface_voxels) return DLV_EINVAL;
-    if (Zb < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_shape: empty volume");
+    DLV_TRY(check_volume(ctx, "cc_shape", Zb, Y, X));
     if (nz < 1 || z_first < 0 || (long long)z_first + nz > Zb || z_abs0 < 0)
         return dlv_fail(ctx, DLV_EINVAL, "cc_shape: planes [%d, %d + %d) at absolute z %d do not lie in a buffer of %d planes", z_first,
                         z_first, nz, z_abs0, Zb);
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_shape: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_label_count(ctx, "cc_shape", n));
     if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "cc_shape: labels must be 4-byte aligned");
     if ((long long)z_abs0 + Zb > 65536 || Y > 65536 || X > 65536) return dlv_fail(ctx, DLV_EUNSUP, "bounding boxes are uint16");
     DLV_HIP(ctx, hipSetDevice(ctx->device));

@@ -11,29 +11,21 @@
 // labels within distance r of v only, which is what lets a slab with r more planes on either side give the slab's exact S.
 // Integer work only, one writer per output voxel, no atomics: the result is exact and independent of scheduling.
 #include "common.h"
+#include "cc_check.h"
+#include "cc_tile.h"
 
 #include <algorithm>
 
 namespace {
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
-typedef u32 u32x2_t __attribute__((ext_vector_type(2)));
-
-constexpr int TX = 64, TY = 8, TZ = 8;         // the voxels a workgroup writes: whole 256-byte runs in x
-constexpr int QX = TX / 4;                     // quads per row
-constexpr int PITCH = TX + 8;                  // LDS row: interior at [4, 4 + TX) (16-byte aligned), the halo voxels at 3 and 4 + TX
-constexpr int ROWS = (TZ + 2) * (TY + 2);      // the tile and its one-voxel halo
-constexpr u32 NONE = 0xffffffffu;              // background while the minimum is taken
+constexpr u32 NONE = 0xffffffffu;  // background while the minimum is taken
 
 __device__ __forceinline__ u32 min3(u32 a, u32 b, u32 c) { return min(a, min(b, c)); }
 
 // One expansion step: dst = E_{k+1} of src = E_k, or with FINAL the shell S of the last step.  A workgroup of 256 threads owns
-// the TZ x TY x TX voxels at (blockIdx.z, .y, .x).  It stages them with their halo in LDS, 0 as NONE, voxels outside the
-// volume as NONE - rows that start on a 16-byte boundary with 16-byte loads, the others (with an odd X the alignment changes
-// from row to row) and the quad across the end of a row element by element.  A tile whose input is all background, halo
-// included, writes nothing: its output is zero in dst already (the launcher's note).  Otherwise every thread takes quads of
+// the TZ x TY x TX voxels at (blockIdx.z, .y, .x).  It stages them with their halo in LDS (cc_tile.h), 0 as NONE, voxels outside
+// the volume as NONE.  A tile whose input is all background, halo included, writes nothing: its output is zero in dst already
+// (the launcher's note).  Otherwise every thread takes quads of
 // four voxels along x: for a quad that holds a background voxel it reads the 9 rows around it (6 values each: one 16-byte
 // read and the two neighbours) and folds the 3 x 3 x 3 minima.  FINAL: only voxels that are background in `labels` (src itself
 // when radius is 1) are kept, and only where raw is not 0; raw (NULL: no such condition) is read just for the quads that
@@ -43,30 +35,18 @@ __global__ void __launch_bounds__(256) cc_shell_sweep_kernel(const u32* __restri
                                                              const unsigned short* __restrict__ raw, int Z, int Y, int X,
                                                              long long pitch_y, long long pitch_z, u32* __restrict__ dst) {
     __shared__ __attribute__((aligned(16))) u32 tile[ROWS * PITCH];
-    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY, z0 = blockIdx.z * TZ;
+    const TileAt t(Z, Y, X);
     u32 seen = 0;
     for (int i = threadIdx.x; i < ROWS * QX; i += 256) {
         const int row = i / QX, q = i % QX;
-        const int z = z0 - 1 + row / (TY + 2), y = y0 - 1 + row % (TY + 2), x = x0 + 4 * q;
-        u32x4_t v = {0, 0, 0, 0};
-        if (z >= 0 && z < Z && y >= 0 && y < Y && x < X) {
-            const u32* p = src + ((u64)z * Y + y) * (u64)X + x;
-            if (x + 4 <= X && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-                v = *reinterpret_cast<const u32x4_t*>(p);
-            } else {
-                v.x = p[0];
-                if (x + 1 < X) v.y = p[1];
-                if (x + 2 < X) v.z = p[2];
-                if (x + 3 < X) v.w = p[3];
-            }
-        }
+        u32x4_t v = tile_quad_of(src, t, row, q);
         seen |= v.x | v.y | v.z | v.w;
         v.x = v.x ? v.x : NONE; v.y = v.y ? v.y : NONE; v.z = v.z ? v.z : NONE; v.w = v.w ? v.w : NONE;
-        *reinterpret_cast<u32x4_t*>(tile + row * PITCH + 4 + 4 * q) = v;
+        *reinterpret_cast<u32x4_t*>(tile + tile_word(row, q)) = v;
     }
     for (int i = threadIdx.x; i < ROWS * 2; i += 256) {
         const int row = i >> 1, right = i & 1;
-        const int z = z0 - 1 + row / (TY + 2), y = y0 - 1 + row % (TY + 2), x = right ? x0 + TX : x0 - 1;
+        const int z = t.z0 - 1 + row / (TY + 2), y = t.y0 - 1 + row % (TY + 2), x = right ? t.x0 + TX : t.x0 - 1;
         u32 v = 0;
         if (z >= 0 && z < Z && y >= 0 && y < Y && x >= 0 && x < X) v = src[((u64)z * Y + y) * (u64)X + x];
         seen |= v;
@@ -76,11 +56,9 @@ __global__ void __launch_bounds__(256) cc_shell_sweep_kernel(const u32* __restri
 
     for (int i = threadIdx.x; i < TZ * TY * QX; i += 256) {
         const int q = i % QX, oy = (i / QX) % TY, oz = i / (QX * TY);
-        const int z = z0 + oz, y = y0 + oy, x = x0 + 4 * q;
+        const int z = t.z0 + oz, y = t.y0 + oy, x = t.x0 + 4 * q;
         if (z >= Z || y >= Y || x >= X) continue;
-        const u64 at = ((u64)z * Y + y) * (u64)X + x;
-        const bool whole = x + 4 <= X;
-        const u32x4_t cen = *reinterpret_cast<const u32x4_t*>(tile + ((oz + 1) * (TY + 2) + oy + 1) * PITCH + 4 + 4 * q);
+        const u32x4_t cen = *reinterpret_cast<const u32x4_t*>(tile + tile_word(tile_row(oz, oy), q));
         u32 e[4] = {cen.x, cen.y, cen.z, cen.w};  // E_{k+1}, NONE for 0
         if (e[0] == NONE || e[1] == NONE || e[2] == NONE || e[3] == NONE) {
             u32 m[4] = {NONE, NONE, NONE, NONE};
@@ -106,21 +84,15 @@ __global__ void __launch_bounds__(256) cc_shell_sweep_kernel(const u32* __restri
         } else {
             bool bg[4] = {cen.x == NONE, cen.y == NONE, cen.z == NONE, cen.w == NONE};  // background in L
             if (labels != src) {  // (uniform) radius > 1: src is E_{r-1}, the cells are in `labels`
-                const u32* p = labels + at;
-                if (whole && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-                    const u32x4_t l = *reinterpret_cast<const u32x4_t*>(p);
-                    bg[0] = l.x == 0; bg[1] = l.y == 0; bg[2] = l.z == 0; bg[3] = l.w == 0;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) bg[j] = x + j < X ? p[j] == 0 : false;
-                }
+                const u32x4_t l = tile_quad_of(labels, t, tile_row(oz, oy), q);  // (0 beyond the end of the row: not kept below)
+                bg[0] = l.x == 0; bg[1] = l.y == 0; bg[2] = l.z == 0; bg[3] = l.w == 0;
             }
             bool keep[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) keep[j] = bg[j] && e[j] != NONE && x + j < X;
             if (raw && (keep[0] || keep[1] || keep[2] || keep[3])) {
                 const unsigned short* p = raw + (u64)z * (u64)pitch_z + (u64)y * (u64)pitch_y + x;
-                if (whole && (reinterpret_cast<uintptr_t>(p) & 7) == 0) {
+                if (x + 4 <= X && (reinterpret_cast<uintptr_t>(p) & 7) == 0) {
                     const u32x2_t u = *reinterpret_cast<const u32x2_t*>(p);
                     keep[0] = keep[0] && (u.x & 0xffffu) != 0; keep[1] = keep[1] && (u.x >> 16) != 0;
                     keep[2] = keep[2] && (u.y & 0xffffu) != 0; keep[3] = keep[3] && (u.y >> 16) != 0;
@@ -132,20 +104,8 @@ __global__ void __launch_bounds__(256) cc_shell_sweep_kernel(const u32* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) out[j] = keep[j] ? e[j] : 0u;
         }
-        u32* p = dst + at;
-        if (whole && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            *reinterpret_cast<u32x4_t*>(p) = u32x4_t{out[0], out[1], out[2], out[3]};
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (x + j < X) p[j] = out[j];
-        }
+        tile_store_quad(dst + ((u64)z * Y + y) * (u64)X + x, x, X, u32x4_t{out[0], out[1], out[2], out[3]});
     }
-}
-
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + bytes && pb < pa + bytes;
 }
 
 }  // namespace
@@ -155,21 +115,19 @@ extern "C" int dlv_cc_shell_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const 
     if (!ctx) return DLV_EINVAL;
     if (!labels_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: labels_dev is NULL");
     if (!shell_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: shell_dev is NULL");
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: empty volume");
+    DLV_TRY(check_volume(ctx, "cc_shell", Z, Y, X));
     if (radius < 1 || radius > 16) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: radius %d is outside 1..16", radius);
     if (radius > 1 && !scratch_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: scratch_dev is NULL with radius %d (needed above 1)", radius);
-    if (raw_dev && (raw_pitch_y < X || raw_pitch_z / Y < raw_pitch_y))
-        return dlv_fail(ctx, DLV_EINVAL, "cc_shell: raw pitches (%lld, %lld) do not hold rows of %d and planes of %d rows",
-                        (long long)raw_pitch_z, (long long)raw_pitch_y, X, Y);
+    if (raw_dev) DLV_TRY(check_raw_pitches(ctx, "cc_shell", Y, X, raw_pitch_y, raw_pitch_z));
     if (((uintptr_t)labels_dev & 3) || ((uintptr_t)shell_dev & 3) || ((uintptr_t)scratch_dev & 3) || ((uintptr_t)raw_dev & 1))
         return dlv_fail(ctx, DLV_EINVAL, "cc_shell: labels, shell and scratch must be 4-byte aligned, raw 2-byte aligned");
-    const dim3 grid((X + TX - 1) / TX, (Y + TY - 1) / TY, (Z + TZ - 1) / TZ);
-    if (grid.y > 65535u || grid.z > 65535u) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: a volume of %d x %d x %d exceeds the launch grid", Z, Y, X);
+    const dim3 grid = tile_grid(Z, Y, X);
+    DLV_TRY(check_tile_grid(ctx, "cc_shell", grid, Z, Y, X));
     const u64 nvox = (u64)Z * Y * X;
     const size_t bytes = (size_t)nvox * 4;
-    if (overlap(shell_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: shell_dev overlaps labels_dev");
-    if (scratch_dev && overlap(scratch_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: scratch_dev overlaps labels_dev");
-    if (scratch_dev && overlap(scratch_dev, shell_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: scratch_dev overlaps shell_dev");
+    if (ranges_overlap(shell_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: shell_dev overlaps labels_dev");
+    if (scratch_dev && ranges_overlap(scratch_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: scratch_dev overlaps labels_dev");
+    if (scratch_dev && ranges_overlap(scratch_dev, shell_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_shell: scratch_dev overlaps shell_dev");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     // Step i = 1..radius writes shell_dev when radius - i is even, scratch_dev otherwise, and reads what step i - 1 wrote
     // (step 1: the labels).  Both buffers start as zeros and a tile without input writes nothing: the support of E_k only

@@ -15,19 +15,13 @@
 // never pending.  Integer work only; one writer per voxel in the sweeps, and the tables are written with atomicMin / atomicAdd
 // or by writers that agree: the result is exact and independent of scheduling.
 #include "common.h"
+#include "cc_check.h"
+#include "cc_tile.h"  // (the tile of the growth)
 
 #include <algorithm>
 
 namespace {
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-typedef u32 u32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int TX = 64, TY = 8, TZ = 8;     // the voxels a workgroup of the growth writes (cc_shell.hip's tile)
-constexpr int QX = TX / 4;                 // quads per row
-constexpr int PITCH = TX + 8;              // LDS row: interior at [4, 4 + TX) (16-byte aligned), the halo voxels at 3 and 4 + TX
-constexpr int ROWS = (TZ + 2) * (TY + 2);  // the tile and its one-voxel halo
 constexpr u32 NONE = 0xffffffffu;          // "no core reaches" while the minimum is taken
 constexpr u32 SKIP = 0xffffffffu;          // G of a voxel whose label is not split: never pending, never a neighbour of a pending voxel
 constexpr int BATCH = 8;                   // growth steps between two read-backs of the change flags
@@ -150,34 +144,9 @@ __global__ void __launch_bounds__(256) split_grow_kernel(const u32* __restrict__
     const u32 st = state[tile];  // (workgroup-uniform: written by this tile's workgroup of the step before)
     if (st == T_DONE) return;
     const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY, z0 = blockIdx.z * TZ;
-
-    // quad q of LDS row `row` (the voxels x0 + 4q .. + 3 of a row of the tile or of its halo) from a volume, 0 outside it
-    auto quad_of = [&](const u32* __restrict__ vol, int row, int q) -> u32x4_t {
-        const int z = z0 - 1 + row / (TY + 2), y = y0 - 1 + row % (TY + 2), x = x0 + 4 * q;
-        u32x4_t v = {0, 0, 0, 0};
-        if (z >= 0 && z < Z && y >= 0 && y < Y && x < X) {
-            const u32* p = vol + ((u64)z * Y + y) * (u64)X + x;
-            if (x + 4 <= X && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-                v = *reinterpret_cast<const u32x4_t*>(p);
-            } else {
-                v.x = p[0];
-                if (x + 1 < X) v.y = p[1];
-                if (x + 2 < X) v.z = p[2];
-                if (x + 3 < X) v.w = p[3];
-            }
-        }
-        return v;
-    };
-    auto store_quad = [&](u32* p, int x, u32x4_t v) {  // the voxels of a quad that lie inside the row
-        if (x + 4 <= X && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            *reinterpret_cast<u32x4_t*>(p) = v;
-        } else {
-            p[0] = v.x;
-            if (x + 1 < X) p[1] = v.y;
-            if (x + 2 < X) p[2] = v.z;
-            if (x + 3 < X) p[3] = v.w;
-        }
-    };
+    const TileAt t(Z, Y, X);
+    auto quad_of = [&](const u32* __restrict__ vol, int row, int q) -> u32x4_t { return tile_quad_of(vol, t, row, q); };
+    auto store_quad = [&](u32* p, int x, u32x4_t v) { tile_store_quad(p, x, X, v); };
     auto carry = [&]() {  // dst = src on the tile's own voxels
         for (int i = threadIdx.x; i < TZ * TY * QX; i += 256) {
             const int q = i % QX, oy = (i / QX) % TY, oz = i / (QX * TY);
@@ -299,13 +268,6 @@ __global__ void __launch_bounds__(256) split_apply_kernel(u32* __restrict__ L, c
     }
 }
 
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + bytes && pb < pa + bytes;
-}
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int depth, int64_t min_core,
@@ -314,20 +276,20 @@ extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y
     if (!ctx) return DLV_EINVAL;
     if (!labels_dev || !work_a_dev || !work_b_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_split: labels_dev, work_a_dev or work_b_dev is NULL");
     if (!n_out || !n_split_out || !parent_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_split: n_out, n_split_out or parent_dev is NULL");
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_split: empty volume");
+    DLV_TRY(check_volume(ctx, "cc_split", Z, Y, X));
     if (depth < 1 || depth > 16) return dlv_fail(ctx, DLV_EINVAL, "cc_split: depth %d is outside 1..16", depth);
     if (min_core < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_split: min_core %lld is below 1", (long long)min_core);
     if (((uintptr_t)labels_dev & 3) || ((uintptr_t)work_a_dev & 3) || ((uintptr_t)work_b_dev & 3) || ((uintptr_t)parent_dev & 3))
         return dlv_fail(ctx, DLV_EINVAL, "cc_split: labels, work_a, work_b and parent must be 4-byte aligned");
-    const dim3 grid((X + TX - 1) / TX, (Y + TY - 1) / TY, (Z + TZ - 1) / TZ);
-    if (grid.y > 65535u || grid.z > 65535u) return dlv_fail(ctx, DLV_EINVAL, "cc_split: a volume of %d x %d x %d exceeds the launch grid", Z, Y, X);
+    const dim3 grid = tile_grid(Z, Y, X);
+    DLV_TRY(check_tile_grid(ctx, "cc_split", grid, Z, Y, X));
     const u64 nvox = (u64)Z * Y * X;
     if (nvox > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "cc_split: volumes above 2^32 voxels need 64-bit labels");
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_split: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_label_count(ctx, "cc_split", n));
     const size_t bytes = (size_t)nvox * 4;
-    if (overlap(work_a_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_a_dev overlaps labels_dev");
-    if (overlap(work_b_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_b_dev overlaps labels_dev");
-    if (overlap(work_b_dev, work_a_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_b_dev overlaps work_a_dev");
+    if (ranges_overlap(work_a_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_a_dev overlaps labels_dev");
+    if (ranges_overlap(work_b_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_b_dev overlaps labels_dev");
+    if (ranges_overlap(work_b_dev, work_a_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_b_dev overlaps work_a_dev");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     const int flat = (int)std::min<u64>((nvox + 255) / 256, (u64)256 * 64);  // the grid-stride kernels over the voxels
     auto rows_grid = [](u64 rows) { return dim3((unsigned)std::min<u64>(std::max<u64>((rows + 255) / 256, 1), (u64)256 * 32)); };
@@ -363,11 +325,11 @@ extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y
     // tables: comp (M + 1), cores (n + 1), first (M + n + 1), the tile states, the change flags of a batch, two words
     // (the labels that are split, "a label above n")
     const u64 ntiles = (u64)grid.x * grid.y * grid.z;
-    const size_t comp_off = 0, cores_off = al256(comp_off + ((size_t)M + 1) * 4), first_off = al256(cores_off + ((size_t)n + 1) * 4);
-    const size_t state_off = al256(first_off + ((size_t)M + n + 1) * 4), flags_off = al256(state_off + (size_t)ntiles * 4);
-    const size_t word_off = al256(flags_off + BATCH * 4), total = word_off + 256;
+    WsCarve c;
+    const size_t comp_off = c.take(((size_t)M + 1) * 4), cores_off = c.take(((size_t)n + 1) * 4), first_off = c.take(((size_t)M + n + 1) * 4);
+    const size_t state_off = c.take((size_t)ntiles * 4), flags_off = c.take(BATCH * 4), word_off = c.take(256);
     char* ws;
-    DLV_TRY(dlv_ws_get(ctx, WS_MISC, total, (void**)&ws));
+    DLV_TRY(dlv_ws_get(ctx, WS_MISC, c.end, (void**)&ws));
     u32 *comp = (u32*)(ws + comp_off), *cores = (u32*)(ws + cores_off), *first = (u32*)(ws + first_off);
     u32 *state = (u32*)(ws + state_off), *flags = (u32*)(ws + flags_off), *word = (u32*)(ws + word_off);
     DLV_HIP(ctx, hipMemsetAsync(ws, 0, first_off, ctx->stream));                              // comp, cores

@@ -3,6 +3,7 @@
 // Replaces cc3d.statistics(..., no_slice_conversion=True) (count_blobs.py:85) on the labels of dlv_ccl26_dev (ccl.hip).
 // Integer work only: results are bit-exact and independent of scheduling.  Both kernels aggregate as cc_fold.h describes.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
 
 #include <algorithm>
@@ -279,7 +280,7 @@ int dlv_cc_stats_raw_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y,
 
 int dlv_cc_counts_dev(dlv_ctx* ctx, const uint32_t* labels_dev, uint64_t nvox, uint64_t n, uint32_t* counts_dev) {
     if (!ctx || !labels_dev || !counts_dev) return DLV_EINVAL;
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_counts: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_label_count(ctx, "cc_counts", n));
     if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "labels must be 4-byte aligned");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     DLV_HIP(ctx, hipMemsetAsync(counts_dev, 0, ((size_t)n + 1) * 4, ctx->stream));

@@ -10,12 +10,11 @@
 // compression, then a raster-order renumbering of the roots by a two-level prefix sum.  Integer
 // work only: results are bit-exact and independent of scheduling.
 #include "common.h"
+#include "cc_check.h"
+#include "dev_scan.h"
 #include <cstdlib>
 
 namespace {
-
-typedef unsigned int u32;
-typedef unsigned long long u64;
 
 __device__ __forceinline__ u32 uf_find(const u32* __restrict__ L, u32 i) {
     u32 p;
@@ -238,23 +237,6 @@ __global__ void __launch_bounds__(256) ccl_compress_kernel(const unsigned short*
 constexpr int RPT = 16;                 // voxels per thread in the renumbering kernels
 constexpr int RCHUNK = 256 * RPT;       // voxels per block
 
-__device__ __forceinline__ int block_excl_scan(int v, int* total) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < wave; ++k) base += wsum[k];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return base + incl - v;
-}
-
 __global__ void __launch_bounds__(256) ccl_count_roots_kernel(const unsigned short* __restrict__ bm, const u32* __restrict__ L,
                                                               u64 n, u32* __restrict__ counts) {
     const u64 base = (u64)blockIdx.x * RCHUNK + (u64)threadIdx.x * RPT;
@@ -268,64 +250,6 @@ __global__ void __launch_bounds__(256) ccl_count_roots_kernel(const unsigned sho
     int total;
     block_excl_scan(c, &total);
     if (threadIdx.x == 0) counts[blockIdx.x] = (u32)total;
-}
-
-// exclusive scan of the per-chunk root counts in three coalesced steps (a single block walking 500 k counts with one
-// strided stream per thread took 0.9 ms of a 9 ms labelling): sums of 1024-count groups, a one-block scan of the group sums
-// (counts[nb] receives the total), then every group scans its own counts
-constexpr int SGRP = 1024;
-__global__ void __launch_bounds__(256) ccl_scan_sums_kernel(const u32* __restrict__ counts, u64 nb, u32* __restrict__ gsum) {
-    const u64 g0 = (u64)blockIdx.x * SGRP;
-    u32 s = 0;
-    for (int i = threadIdx.x; i < SGRP; i += 256)
-        if (g0 + i < nb) s += counts[g0 + i];
-    int total;
-    block_excl_scan((int)s, &total);
-    if (threadIdx.x == 0) gsum[blockIdx.x] = (u32)total;
-}
-__global__ void __launch_bounds__(1024) ccl_scan_groups_kernel(u32* __restrict__ gsum, u64 ng, u32* __restrict__ total_out) {
-    __shared__ u64 part[1024];
-    const u64 per = (ng + 1023) / 1024;
-    const u64 b0 = min((u64)threadIdx.x * per, ng), b1 = min(b0 + per, ng);
-    u64 s = 0;
-    for (u64 i = b0; i < b1; ++i) s += gsum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 run = 0;
-        for (int k = 0; k < 1024; ++k) {
-            const u64 v = part[k];
-            part[k] = run;
-            run += v;
-        }
-        *total_out = (u32)run;  // N <= 2^32-1 by construction (labels are uint32)
-    }
-    __syncthreads();
-    u64 run = part[threadIdx.x];
-    for (u64 i = b0; i < b1; ++i) {
-        const u32 v = gsum[i];
-        gsum[i] = (u32)run;
-        run += v;
-    }
-}
-__global__ void __launch_bounds__(256) ccl_scan_apply_kernel(u32* __restrict__ counts, u64 nb, const u32* __restrict__ gsum) {
-    const u64 g0 = (u64)blockIdx.x * SGRP;
-    u32 v[SGRP / 256];
-    int mine = 0;
-#pragma unroll
-    for (int k = 0; k < SGRP / 256; ++k) {  // thread t owns the 4 consecutive counts 4t .. 4t+3 of the group
-        const u64 i = g0 + (u64)threadIdx.x * (SGRP / 256) + k;
-        v[k] = i < nb ? counts[i] : 0u;
-        mine += (int)v[k];
-    }
-    int total;
-    u32 run = gsum[blockIdx.x] + (u32)block_excl_scan(mine, &total);
-#pragma unroll
-    for (int k = 0; k < SGRP / 256; ++k) {
-        const u64 i = g0 + (u64)threadIdx.x * (SGRP / 256) + k;
-        if (i < nb) counts[i] = run;
-        run += v[k];
-    }
 }
 
 // The union-find runs IN the label volume (round 6: L == labels; the separate parent array was 4 bytes per voxel of scratch -
@@ -522,7 +446,7 @@ __global__ void __launch_bounds__(256) relabel_lut_kernel(u32* __restrict__ labe
 // ---- size filter (count_blobs' min_size / max_size; cc3d.dust): keep flags from the voxel count per label (dlv_cc_counts_dev,
 // cc_stats.hip), order-preserving renumbering of the kept labels through a lookup table ---------------------------------------
 // The lookup table of the size filter is made in three launches over the same n + 1 rows, in this order: size_keep_kernel writes
-// the keep flags, the ccl_scan_* kernels turn them into their exclusive prefix sum (the number of kept labels below each label),
+// the keep flags, the dev_scan_* kernels (dev_scan.h) turn them into their exclusive prefix sum (the number of kept labels below each label),
 // size_lut_kernel turns that into the new label.  Both kernels ask size_keeps(), so that they cannot disagree about a label.
 __device__ __forceinline__ bool size_keeps(const u32* __restrict__ counts, u64 l, u64 lo, u64 hi) {
     // label 1..n whose voxel count lies in [lo, hi]; label 0 is the background: never kept
@@ -551,14 +475,13 @@ int ccl_ws_get(dlv_ctx* ctx, u64 n, CclWs& w) {
     w.nb = (n + RCHUNK - 1) / RCHUNK;
     w.nch = (n + 15) / 16;
     char* ws;
-    const size_t counts_off = 0;
-    const size_t gsum_off = (counts_off + (size_t)(w.nb + 1) * 4 + 255) & ~(size_t)255;
-    const size_t bm_off = (gsum_off + (size_t)((w.nb + SGRP - 1) / SGRP + 1) * 4 + 255) & ~(size_t)255;
-    const size_t rb_off = (bm_off + (size_t)(w.nch + 4) * 2 + 255) & ~(size_t)255;
-    const size_t list_off = (rb_off + (size_t)(w.nch + 4) * 2 + 255) & ~(size_t)255;  // [list_n, pad, list[nch]]
-    DLV_TRY(dlv_ws_get(ctx, WS_CCL, list_off + 256 + (size_t)w.nch * 4 + 256, (void**)&ws));
-    w.list_n = (u32*)(ws + list_off);
-    w.list = (u32*)(ws + list_off + 256);
+    WsCarve c;
+    const size_t counts_off = c.take((size_t)(w.nb + 1) * 4), gsum_off = c.take((size_t)(scan_groups(w.nb) + 1) * 4);
+    const size_t bm_off = c.take((size_t)(w.nch + 4) * 2), rb_off = c.take((size_t)(w.nch + 4) * 2);
+    const size_t list_n_off = c.take(256), list_off = c.take((size_t)w.nch * 4 + 256);  // [list_n, pad, list[nch]]
+    DLV_TRY(dlv_ws_get(ctx, WS_CCL, c.end, (void**)&ws));
+    w.list_n = (u32*)(ws + list_n_off);
+    w.list = (u32*)(ws + list_off);
     w.rb = (unsigned short*)(ws + rb_off);
     w.counts = (u32*)(ws + counts_off);
     w.gsum = (u32*)(ws + gsum_off);
@@ -572,11 +495,7 @@ int ccl_ws_get(dlv_ctx* ctx, u64 n, CclWs& w) {
 int ccl_number_roots(dlv_ctx* ctx, const CclWs& w, u32* labels, u64 n) {
     hipLaunchKernelGGL(ccl_count_roots_kernel, dim3((unsigned)w.nb), dim3(256), 0, ctx->stream, w.bm, labels, n, w.counts);
     DLV_LAUNCH_CHECK(ctx, "ccl_count_roots_kernel");
-    const u64 ng = (w.nb + SGRP - 1) / SGRP;
-    hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, w.counts, w.nb, w.gsum);
-    hipLaunchKernelGGL(ccl_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, w.gsum, ng, w.counts + w.nb);
-    hipLaunchKernelGGL(ccl_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, w.counts, w.nb, w.gsum);
-    DLV_LAUNCH_CHECK(ctx, "ccl_scan_counts_kernel");
+    DLV_TRY(dev_excl_scan(ctx, w.counts, w.nb, w.counts, w.gsum, w.counts + w.nb, "ccl_scan_counts_kernel"));
     hipLaunchKernelGGL(ccl_assign_roots_kernel, dim3((unsigned)w.nb), dim3(256), 0, ctx->stream, w.bm, labels, n, w.counts, labels, w.rb);
     DLV_LAUNCH_CHECK(ctx, "ccl_assign_roots_kernel");
     return DLV_OK;
@@ -646,7 +565,7 @@ int dlv_ccl26_dev(dlv_ctx* ctx, const uint8_t* mask_dev, int Z, int Y, int X, ui
     ran.init_grid = gs;
     ran.init_per = ccl_init_per(w.nch, (u64)gs);
     ran.blocks = w.nb;
-    ran.groups = (w.nb + SGRP - 1) / SGRP;
+    ran.groups = scan_groups(w.nb);
     const int gl = 256 * 16;  // list kernels: grid-stride over the device-side count
     ran.merge_rows = (aligned && X % 16 == 0) ? 1 : 0;
     if (ran.merge_rows)
@@ -708,20 +627,20 @@ int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, ui
     if (!ctx || !labels_dev || !counts_dev || !n_kept_out) return DLV_EINVAL;
     if (min_size >= 0 && max_size >= 0 && min_size > max_size)
         return dlv_fail(ctx, DLV_EINVAL, "size filter: min_size %lld > max_size %lld", (long long)min_size, (long long)max_size);
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "size filter: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_label_count(ctx, "size filter", n));
     if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "labels must be 4-byte aligned");
     *n_kept_out = n;
     if (min_size < 0 && max_size < 0) return DLV_OK;  // no bound: nothing to do
     if (n == 0 || nvox == 0) return DLV_OK;           // no component: nothing to remove
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     const u64 lo = min_size < 0 ? 0ull : (u64)min_size, hi = max_size < 0 ? ~0ull : (u64)max_size;
-    const u64 rows = n + 1, ng = (rows + SGRP - 1) / SGRP;
+    const u64 rows = n + 1;
     // scratch: the lookup table (n + 1 labels), the sums of its 1024-label groups, the number of kept labels
-    const size_t gsum_off = ((size_t)rows * 4 + 255) & ~(size_t)255;
-    const size_t total_off = (gsum_off + (size_t)(ng + 1) * 4 + 255) & ~(size_t)255;
+    WsCarve c;
+    const size_t lut_off = c.take((size_t)rows * 4), gsum_off = c.take((size_t)(scan_groups(rows) + 1) * 4), total_off = c.take(256);
     char* ws;
-    DLV_TRY(dlv_ws_get(ctx, WS_MISC, total_off + 256, (void**)&ws));
-    u32* lut = (u32*)ws;
+    DLV_TRY(dlv_ws_get(ctx, WS_MISC, c.end, (void**)&ws));
+    u32* lut = (u32*)(ws + lut_off);
     u32* gsum = (u32*)(ws + gsum_off);
     u32* total = (u32*)(ws + total_off);
     // bytes: the volume is read and (where it holds foreground) written back; the table lookups stay in the caches
@@ -729,11 +648,7 @@ int dlv_cc_size_filter_dev(dlv_ctx* ctx, uint32_t* labels_dev, uint64_t nvox, ui
     const int gr = (int)std::min<u64>((rows + 255) / 256, (u64)256 * 32);
     hipLaunchKernelGGL(size_keep_kernel, dim3(gr), dim3(256), 0, ctx->stream, counts_dev, rows, lo, hi, lut);
     DLV_LAUNCH_CHECK(ctx, "size_keep_kernel");
-    // exclusive scan of the flags with the three kernels of the labelling's renumbering (any number of labels)
-    hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, lut, rows, gsum);
-    hipLaunchKernelGGL(ccl_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, gsum, ng, total);
-    hipLaunchKernelGGL(ccl_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, lut, rows, gsum);
-    DLV_LAUNCH_CHECK(ctx, "ccl_scan_counts_kernel");
+    DLV_TRY(dev_excl_scan(ctx, lut, rows, lut, gsum, total, "ccl_scan_counts_kernel"));  // (in place, any number of labels)
     hipLaunchKernelGGL(size_lut_kernel, dim3(gr), dim3(256), 0, ctx->stream, counts_dev, rows, lo, hi, lut);
     DLV_LAUNCH_CHECK(ctx, "size_lut_kernel");
     const u32 head = (u32)std::min<u64>(((16 - ((uintptr_t)labels_dev & 15)) & 15) / 4, nvox);

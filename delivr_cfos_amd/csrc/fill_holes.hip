@@ -34,7 +34,9 @@
 // Measured once on an MI355X (profiles/README.md, "fill_holes"): 1024 x 2048 x 2048, the bench's cell mask (0.22 % foreground, 4121
 // holes) 2.5 ms beside 8.2 ms of dlv_ccl26_dev on the same mask; the same mask with every cell hollowed (494 764 holes) 3.1 ms.
 #include "common.h"
+#include "cc_check.h"
 #include "cc_fold.h"
+#include "dev_scan.h"
 
 #include <algorithm>
 
@@ -42,7 +44,6 @@ namespace {
 
 constexpr int FT = 64;                 // threads per workgroup of the row kernels: one wave, one row at a time
 constexpr u64 FILL_MAX_WG = 256 * 32;  // workgroups per launch; rows beyond that are walked grid-stride
-constexpr int FGRP = 1024;             // rows per scan group
 constexpr u32 EXT_NONE = 1u;           // the extent (first | last << 16) of a row without foreground: first 1 > last 0 covers nothing
 
 __device__ __forceinline__ u32 fh_find(const u32* __restrict__ P, u32 i) {
@@ -138,77 +139,6 @@ __global__ void __launch_bounds__(FT) fill_count_kernel(const uint8_t* __restric
         }
     }
     if (__any(bad) && lane == 0) *bad_flag = 1u;
-}
-
-// ---- exclusive scan of the row counts, in place (counts[nrows] receives the total): ccl.hip's three coalesced steps -------------
-__device__ __forceinline__ u32 fill_block_excl_scan(u32 v, u32* total) {
-    __shared__ u32 wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    u32 base = 0;
-    for (int k = 0; k < wave; ++k) base += wsum[k];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return base + incl - v;
-}
-__global__ void __launch_bounds__(256) fill_scan_sums_kernel(const u32* __restrict__ counts, u64 nrows, u32* __restrict__ gsum) {
-    const u64 g0 = (u64)blockIdx.x * FGRP;
-    u32 s = 0;
-    for (int i = threadIdx.x; i < FGRP; i += 256)
-        if (g0 + i < nrows) s += counts[g0 + i];
-    u32 total;
-    fill_block_excl_scan(s, &total);
-    if (threadIdx.x == 0) gsum[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(1024) fill_scan_groups_kernel(u32* __restrict__ gsum, u64 ng, u32* __restrict__ total_out) {
-    __shared__ u32 part[1024];
-    const u64 per = (ng + 1023) / 1024;
-    const u64 b0 = min((u64)threadIdx.x * per, ng), b1 = min(b0 + per, ng);
-    u32 s = 0;
-    for (u64 i = b0; i < b1; ++i) s += gsum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 run = 0;
-        for (int k = 0; k < 1024; ++k) {
-            const u32 v = part[k];
-            part[k] = run;
-            run += v;
-        }
-        *total_out = run;  // (<= 2^31 gaps)
-    }
-    __syncthreads();
-    u32 run = part[threadIdx.x];
-    for (u64 i = b0; i < b1; ++i) {
-        const u32 v = gsum[i];
-        gsum[i] = run;
-        run += v;
-    }
-}
-__global__ void __launch_bounds__(256) fill_scan_apply_kernel(u32* __restrict__ counts, u64 nrows, const u32* __restrict__ gsum) {
-    const u64 g0 = (u64)blockIdx.x * FGRP;
-    u32 v[FGRP / 256];
-    u32 mine = 0;
-#pragma unroll
-    for (int k = 0; k < FGRP / 256; ++k) {  // thread t owns the 4 consecutive rows 4t .. 4t+3 of the group
-        const u64 i = g0 + (u64)threadIdx.x * (FGRP / 256) + k;
-        v[k] = i < nrows ? counts[i] : 0u;
-        mine += v[k];
-    }
-    u32 total;
-    u32 run = gsum[blockIdx.x] + fill_block_excl_scan(mine, &total);
-#pragma unroll
-    for (int k = 0; k < FGRP / 256; ++k) {
-        const u64 i = g0 + (u64)threadIdx.x * (FGRP / 256) + k;
-        if (i < nrows) counts[i] = run;
-        run += v[k];
-    }
 }
 
 // ---- emit: x0 / x1 / row of every gap at row_start[row] + its rank in the row; parent[node] = node ------------------------------
@@ -418,21 +348,20 @@ extern "C" {
 int dlv_fill_holes_u8_dev(dlv_ctx* ctx, uint8_t* mask_dev, int Z, int Y, int X, uint8_t fill_value, uint64_t* voxels_filled,
                           uint64_t* holes) {
     if (!ctx || !mask_dev || !voxels_filled || !holes) return DLV_EINVAL;
-    if (Z < 1 || Y < 1 || X < 1) return dlv_fail(ctx, DLV_EINVAL, "fill_holes: empty volume");
+    DLV_TRY(check_volume(ctx, "fill_holes", Z, Y, X));
     if (fill_value == 0) return dlv_fail(ctx, DLV_EINVAL, "fill_holes: fill_value 0 is the background");
     if (X > 65536) return dlv_fail(ctx, DLV_EUNSUP, "fill_holes: X = %d, x0 / x1 are uint16", X);
     const u64 nrows = (u64)Z * Y;
     if (nrows > (((u64)1 << 32) / (u64)X)) return dlv_fail(ctx, DLV_EUNSUP, "fill_holes: volumes above 2^32 voxels are not supported");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
-    const u64 ng = (nrows + FGRP - 1) / FGRP;  // (<= 2^22: one workgroup per group in the scan)
     // row table (slot WS_CCL; the labelling that follows takes the slot over): [row_start u32 nrows + 1 | extent u32 nrows |
-    // group sums u32 ng | bad flag u32, holes u32, voxels u64]
-    const size_t ext_off = (((size_t)nrows + 1) * 4 + 255) & ~(size_t)255;
-    const size_t gsum_off = (ext_off + (size_t)nrows * 4 + 255) & ~(size_t)255;
-    const size_t out_off = (gsum_off + (size_t)ng * 4 + 255) & ~(size_t)255;
+    // group sums u32, one per scan group (<= 2^22: one workgroup per group in the scan) | bad flag u32, holes u32, voxels u64]
+    WsCarve c;
+    const size_t rows_off = c.take(((size_t)nrows + 1) * 4), ext_off = c.take((size_t)nrows * 4);
+    const size_t gsum_off = c.take((size_t)scan_groups(nrows) * 4), out_off = c.take(16);
     char* ws;
-    DLV_TRY(dlv_ws_get(ctx, WS_CCL, out_off + 16, (void**)&ws));
-    u32* row_start = (u32*)ws;
+    DLV_TRY(dlv_ws_get(ctx, WS_CCL, c.end, (void**)&ws));
+    u32* row_start = (u32*)(ws + rows_off);
     u32* ext = (u32*)(ws + ext_off);
     u32* gsum = (u32*)(ws + gsum_off);
     u32* bad_flag = (u32*)(ws + out_off);
@@ -443,10 +372,8 @@ int dlv_fill_holes_u8_dev(dlv_ctx* ctx, uint8_t* mask_dev, int Z, int Y, int X, 
     DlvProf pr(ctx, "fill_holes", 0.0, (double)nrows * X);
     hipLaunchKernelGGL(fill_count_kernel, dim3(grows), dim3(FT), 0, ctx->stream, mask_dev, nrows, X, (u32)fill_value, row_start, ext, bad_flag);
     DLV_LAUNCH_CHECK(ctx, "fill_count_kernel");
-    hipLaunchKernelGGL(fill_scan_sums_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, row_start, nrows, gsum);
-    hipLaunchKernelGGL(fill_scan_groups_kernel, dim3(1), dim3(1024), 0, ctx->stream, gsum, ng, row_start + nrows);
-    hipLaunchKernelGGL(fill_scan_apply_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, row_start, nrows, gsum);
-    DLV_LAUNCH_CHECK(ctx, "fill_scan_kernel");
+    // the counts become row_start in place, row_start[nrows] the number of gaps (<= 2^31)
+    DLV_TRY(dev_excl_scan(ctx, row_start, nrows, row_start, gsum, row_start + nrows, "fill_scan_kernel"));
     u32 bad = 0, n_gaps = 0;
     DLV_HIP(ctx, hipMemcpyAsync(&bad, bad_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     DLV_HIP(ctx, hipMemcpyAsync(&n_gaps, row_start + nrows, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -456,12 +383,12 @@ int dlv_fill_holes_u8_dev(dlv_ctx* ctx, uint8_t* mask_dev, int Z, int Y, int X, 
     *holes = 0;
     if (n_gaps == 0) return DLV_OK;  // no row has background between foreground: no hole
     // gap table (slot WS_MISC): [parent u32 n_gaps + 1 | row u32 n_gaps | x0 u16 n_gaps | x1 u16 n_gaps]
-    const size_t grow_off = (((size_t)n_gaps + 1) * 4 + 255) & ~(size_t)255;
-    const size_t x0_off = (grow_off + (size_t)n_gaps * 4 + 255) & ~(size_t)255;
-    const size_t x1_off = (x0_off + (size_t)n_gaps * 2 + 255) & ~(size_t)255;
+    WsCarve g;
+    const size_t parent_off = g.take(((size_t)n_gaps + 1) * 4), grow_off = g.take((size_t)n_gaps * 4);
+    const size_t x0_off = g.take((size_t)n_gaps * 2), x1_off = g.take((size_t)n_gaps * 2);
     char* gs;
-    DLV_TRY(dlv_ws_get(ctx, WS_MISC, x1_off + (size_t)n_gaps * 2, (void**)&gs));
-    u32* parent = (u32*)gs;
+    DLV_TRY(dlv_ws_get(ctx, WS_MISC, g.end, (void**)&gs));
+    u32* parent = (u32*)(gs + parent_off);
     u32* grow = (u32*)(gs + grow_off);
     unsigned short* x0 = (unsigned short*)(gs + x0_off);
     unsigned short* x1 = (unsigned short*)(gs + x1_off);
@@ -489,7 +416,7 @@ int dlv_fill_holes_u8_dev(dlv_ctx* ctx, uint8_t* mask_dev, int Z, int Y, int X, 
 int dlv_cc_count_marked_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint8_t* mask_dev, uint64_t nvox, uint64_t n, uint8_t value,
                             uint32_t* counts_dev) {
     if (!ctx || !labels_dev || !mask_dev || !counts_dev) return DLV_EINVAL;
-    if (n >= 0xffffffffull) return dlv_fail(ctx, DLV_EINVAL, "cc_count_marked: n = %llu does not fit the uint32 labels", (unsigned long long)n);
+    DLV_TRY(check_label_count(ctx, "cc_count_marked", n));
     if ((uintptr_t)labels_dev & 3) return dlv_fail(ctx, DLV_EINVAL, "labels must be 4-byte aligned");
     DLV_HIP(ctx, hipSetDevice(ctx->device));
     DLV_HIP(ctx, hipMemsetAsync(counts_dev, 0, ((size_t)n + 1) * 4, ctx->stream));

@@ -9,6 +9,7 @@
 // The opt-in painting by label instead of by box - out[v] = value[label[v]], from the dense labels or their run-length coding - is
 // cc_paint.hip (settings["mi355x"]["paint_from"] = "labels").
 #include "common.h"
+#include "cc_types.h"
 
 // scipy-exact fp64 arithmetic below (Gaussian filter, distance transform): no a*b+c may become an fma - HIP contracts by
 // default and the __d*_rn "intrinsics" are plain operators in its headers
@@ -16,9 +17,6 @@
 
 
 namespace {
-
-typedef unsigned int u32;
-typedef unsigned long long u64;
 
 constexpr long long PAINT_BIG = 1 << 16;  // boxes above this volume get a launch of their own
 

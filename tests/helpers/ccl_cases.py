@@ -13,7 +13,7 @@ OFFSETS26 = [o for o in itertools.product((-1, 0, 1), repeat=3) if o != (0, 0, 0
 PRECEDING13 = [o for o in OFFSETS26 if o < (0, 0, 0)]
 assert len(PRECEDING13) == 13
 
-GROUP_VOXELS = 1024 * 4096  # voxels of one group of the two-level scan: 1024 blocks of 4096 (csrc/ccl.hip: SGRP, RCHUNK)
+GROUP_VOXELS = 1024 * 4096  # voxels of one group of the two-level scan: 1024 blocks of 4096 (csrc/dev_scan.h: SCAN_GROUP, csrc/ccl.hip: RCHUNK)
 
 
 def _done(mask):

@@ -159,7 +159,7 @@ def _groups_specks():
 
 @pytest.mark.parametrize("build", [_groups_lattice, _groups_random, _groups_specks], ids=["lattice", "random4pc", "boundary_specks"])
 def test_renumbering_across_two_scan_groups(eng, build):
-    """The two-level scan with two groups (ccl_scan_sums / ccl_scan_groups / ccl_scan_apply): the labels of the second group start
+    """The two-level scan with two groups (dev_scan_sums / dev_scan_groups / dev_scan_apply, csrc/dev_scan.h): the labels of the second group start
     at the first group's total.  Smallest shape: a group is 1024 blocks of 4096 voxels = 4,194,304 voxels, so 17 planes of 512 x 512
     are the fewest whole planes with a second group (18 for the lattice: 589,824 labels, 1152 blocks).  boundary_specks: nothing
     but voxel 4,194,303 and voxel 4,194,304 - the second group starts at 1, not at 0."""
@@ -361,7 +361,7 @@ def many_labels():
 @pytest.mark.parametrize("head", [0, 1, 3])
 def test_size_filter_over_more_than_2_20_labels(eng, many_labels, head):
     """dlv_cc_size_filter_dev with bounds [2, 2] on 1,100,000 labels: its lookup table is the scan over n + 1 rows, and
-    ccl_scan_groups_kernel gives a thread more than one group (per > 1) only above 1024 groups of 1024 rows = 2^20 rows - 1,100,001
+    dev_scan_groups_kernel gives a thread more than one group (per > 1) only above 1024 groups of 1024 rows = 2^20 rows - 1,100,001
     rows are 1075 groups, per = 2.  head: the volume starts 16 - 4 * head bytes past a 16-byte boundary (relabel_lut_kernel with
     head > 0).  n_kept and the filtered volume equal numpy's cumulative sum over the kept flags."""
     import torch

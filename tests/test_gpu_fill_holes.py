@@ -120,6 +120,19 @@ def test_more_rows_than_workgroups(eng):
     _check(eng, ref.dense_random((34, 250, 35), 0.75, 5))
 
 
+def test_more_scan_groups_than_threads_of_the_one_block_step(eng):
+    """(1030, 1024, 5): 1 054 720 rows are 1030 scan groups of 1024 rows for the 1024 threads of the scan's one-block step, so a
+    thread owns two groups (thread 514 the last two, thread 515 and above none) - with the row table scanned in place.  X = 5
+    keeps the volume small and puts the rows at every alignment."""
+    shape = (1030, 1024, 5)
+    groups = -(-shape[0] * shape[1] // 1024)
+    assert groups == 1030 > 1024 and -(-groups // 1024) == 2 and groups // 2 == 515
+    mask = ref.dense_random(shape, 0.75, 11)
+    runs = mask[:, :, 0].astype(np.int64) + (mask[:, :, 1:] & ~mask[:, :, :-1]).sum(axis=2)
+    assert np.maximum(runs - 1, 0).sum() == 528289  # the gaps of its rows (a row's foreground runs - 1): what the scan adds up
+    assert _check(eng, mask, voxels=342241) == (342241, 200850)
+
+
 def test_checkerboards(eng):
     # (y + x) even in every plane: X / 2 gaps in every row, every one open along z: nothing is filled, and the call returns
     assert _check(eng, ref.checkerboard(planes=False)) == (0, 0)

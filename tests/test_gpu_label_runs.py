@@ -179,6 +179,23 @@ def test_more_rows_than_workgroups_and_the_degenerate_volumes(eng):
     assert len(runs1["label"]) == 21 and (runs1["x0"] == 0).all() and (runs1["x1"] == 36).all()
 
 
+def test_more_scan_groups_than_threads_of_the_one_block_step(eng):
+    """(1030, 1024, 5): 1 054 720 rows are 1030 scan groups of 1024 rows for the 1024 threads of the scan's one-block step, so a
+    thread owns two groups (thread 514 the last two, thread 515 and above none) - with the 64-bit row_start as the output.  X = 5
+    keeps the volume small and puts the rows at every alignment."""
+    rng = np.random.default_rng(11)
+    shape = (1030, 1024, 5)
+    v = (rng.integers(1, 4, size=shape, dtype=np.uint32) * (rng.random(shape) < 0.45)).astype(np.uint32)
+    rows = shape[0] * shape[1]
+    groups = -(-rows // 1024)
+    assert groups == 1030 > 1024 and -(-groups // 1024) == 2 and groups % 2 == 0 and groups // 2 == 515
+    assert 0.44 < (v != 0).mean() < 0.46 and set(np.unique(v).tolist()) == {0, 1, 2, 3}
+    want = _round_trip(eng, v)
+    per_row = np.diff(want["row_start"].astype(np.int64))
+    assert want["row_start"].dtype == np.uint64 and len(per_row) == rows
+    assert per_row.reshape(groups, 1024).sum(axis=1).min() > 1000  # every group adds to the groups behind it
+
+
 # ---- 4. more than 2^16 runs and labels ---------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def specks(eng):

@@ -17,8 +17,8 @@ import numpy as np
 
 from . import hostio, label_runs
 from .hostlogic import (FILL_VALUE, QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_confidence_csv_text,
-                        cell_holes_csv_text, cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
-                        count_options, csv_name, finish_confidence, finish_intensity, finish_quartiles, finish_shape, finish_shell,
+                        cell_depth_csv_text, cell_holes_csv_text, cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
+                        count_options, csv_name, finish_confidence, finish_depth, finish_intensity, finish_quartiles, finish_shape, finish_shell,
                         finish_shell_quartiles, finish_split, measuring_plan, merge_confidence, merge_intensity, merge_shape,
                         merge_shell)
 
@@ -239,7 +239,7 @@ def _write_table(path_out, folder, brain, text):
 
 def _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file=None):
     """the tables of the opt-in statistics `opts` asks for, and what count_blobs.last_intensity / last_quartiles / last_shape /
-    last_confidence say"""
+    last_confidence / last_depth say"""
     def for_table(shell_keys):  # (shell entries of a cached pickle do not reach the table of a run without the key)
         return stats if opts.shell_radius else {k: v for k, v in stats.items() if k not in shell_keys}
 
@@ -257,6 +257,9 @@ def _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file=None):
     if opts.confidence:
         _write_table(path_out, "cell_confidence", brain, cell_confidence_csv_text(stats, N))
         count_blobs.last_confidence = {"n": int(N), "prob_file": prob_file}
+    if opts.depth is not None:
+        _write_table(path_out, "cell_depth", brain, cell_depth_csv_text(stats, N))
+        count_blobs.last_depth = {"n": int(N), "spacing": tuple(opts.depth)}
     if opts.fill_holes and "hole_voxels" in stats:  # (a cached labelling is not filled: its pickle may lack the key)
         _write_table(path_out, "cell_holes", brain, cell_holes_csv_text(stats, N))
 
@@ -511,7 +514,20 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     leaves the cavities unpainted, "paint_from": "labels" paints them.  A cached labelling - dense or runs - is reused as it is: it is
     NOT filled.  A mask that needs the slab-streamed path is refused (MemoryError), torch.distributed is refused with ValueError on
     every rank: a cavity that crosses a slab cut is closed on neither side.  Off or absent: nothing of this happens, and no new kernel
-    is launched."""
+    is launched.
+
+    ``settings["mi355x"]["depth_stats"]`` true (on its own: no raw volume is opened; ``depth_spacing`` = [wz, wy, wx], integers 1..64,
+    default [1, 1, 1]): how thick every cell is and where its middle lies.  The exact squared Euclidean distance of every voxel of a
+    cell to the nearest voxel outside it - the background, a touching cell and the outside of the volume alike -, in units of the
+    spacing, is taken on the final labels on the device (HipEngine.cc_depth), where shape_stats is measured: after fill, split and
+    filter.  The pickle gains depth_max_sq (uint32), depth_sum_sq and depth_peak_index (uint64), the exact integers, and the derived
+    depth_radius (the radius of the largest inscribed ball), depth_mean_sq, depth_peak (int64 (N+1, 3): z, y, x of the deepest voxel,
+    which always lies inside the cell) and depth_spacing (hostlogic.finish_depth); the table goes to
+    <output_location>/cell_depth/<brain>.csv, ``count_blobs.last_depth`` holds {"n", "spacing"} and ``count_blobs.last_timings``
+    gains depth_s.  Cached labels - dense or decoded runs - are measured too, and a cached pickle without the keys, or with another
+    depth_spacing, is completed.  Needs 8 more bytes of HBM per voxel while it runs; a mask that needs the slab-streamed path is
+    refused (MemoryError).  Under torch.distributed the key is refused with ValueError on every rank: a cell that crosses a slab cut
+    has its nearest outside voxel on another rank.  Off or absent: nothing of this happens, and no new kernel is launched."""
     from .engine import shared_engine
 
     count_blobs.last_filter = None  # set by a run that filtered
@@ -521,6 +537,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
     count_blobs.last_confidence = None  # set by a run with settings["mi355x"]["confidence_stats"]
     count_blobs.last_fill = None  # set by a run that filled holes (settings["mi355x"]["fill_holes"])
+    count_blobs.last_depth = None  # set by a run with settings["mi355x"]["depth_stats"]
     opts = count_options(settings, min_size, max_size)  # (a bad key raises here, before any file is touched)
     split, shell_radius = opts.split, opts.shell_radius
     if opts.bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
@@ -545,6 +562,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['fill_holes'] is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a cavity that crosses a slab cut is closed on neither side, so a Z-slab cannot "
                          "be filled on its own; run step 3 on one device or switch fill_holes off")
+    if sharded and opts.depth is not None:
+        # (as for split_fused: all raise, before any collective, or none does)
+        raise ValueError(f"count_blobs: settings['mi355x']['depth_stats'] is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): a cell that crosses a slab cut has its nearest outside voxel on another "
+                         "rank, so a Z-slab cannot be measured on its own; run step 3 on one device or switch depth_stats off")
     if sharded and opts.runs_file:
         # (as for split_fused: all raise, before any collective, or none does)
         raise ValueError(f"count_blobs: settings['mi355x']['label_file'] = \"runs\" is not available under torch.distributed "
@@ -666,8 +688,8 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
     (hostlogic.CountOptions).  A fresh labelling is split, then filtered, between dlv_ccl26_dev and the label write - the two
     scratch volumes of the split are gone before the raw volume is uploaded, so the two peaks do not add.  The labels - fresh or
     cached - are measured after cc_stats: what hostlogic.measuring_plan finds missing, from one upload of raw_vol (_measure_raw), then
-    the confidence from one upload of prob_vol (_measure_confidence: the raw tensor is gone by then), then the shape accumulators;
-    the pickle is written once, after the last of these."""
+    the confidence from one upload of prob_vol (_measure_confidence: the raw tensor is gone by then), then the shape accumulators,
+    then the depth (HipEngine.cc_depth); the pickle is written once, after the last of these."""
     import time
 
     bounds, split = opts.bounds, opts.split
@@ -864,7 +886,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             if got.shell_quartiles is not None:
                 stats.update(finish_shell_quartiles(*got.shell_quartiles, stats["shell_voxels"], stats["intensity_median"]))
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
-            if not plan & {"confidence", "shape"}:
+            if not plan & {"confidence", "shape", "depth"}:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")
             if opts.quartiles:  # (HipEngine.cc_quantiles is synchronous: its share of the time since the last mark)
@@ -874,15 +896,23 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
             stats.update(finish_confidence(_measure_confidence(eng, labels_dev, prob_vol, N), stats["voxel_counts"], bin_img.shape))
-            if "shape" not in plan:
+            if not plan & {"shape", "depth"}:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
             mark("confidence")
         if "shape" in plan:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
             stats.update(finish_shape(eng.cc_shape(labels_dev, N), stats["voxel_counts"]))
-            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
+            if "depth" not in plan:
+                write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
             mark("shape")
+        if "depth" in plan:
+            if labels_dev is None:
+                labels_dev = cached_labels_to_device()
+            # (the two scratch volumes of the distance map are gone when cc_depth returns)
+            stats.update(finish_depth(eng.cc_depth(labels_dev, N, opts.depth), stats["voxel_counts"], bin_img.shape, opts.depth))
+            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
+            mark("depth")
     except BaseException:
         try:
             wait()  # (do not leave the writer thread behind an error of this one)

@@ -897,6 +897,38 @@ class HipEngine:
         self._leave()
         return out
 
+    def cc_depth(self, labels, n: int, spacing=(1, 1, 1), return_map: bool = False) -> dict:
+        """Per-label depth from the exact label-wise Euclidean distance map (dlv_cc_depth_dev).  labels: int32 (uint32 payload)
+        (Z,Y,X) in HBM, contiguous, not modified.  spacing: (wz, wy, wx), integers 1..64.  D2 of a voxel of a label 1..n is its
+        squared distance, in spacing units, to the nearest voxel of another label, the outside of the volume counting as
+        background; 0 elsewhere.  -> {"depth_max_sq": uint32, "depth_sum_sq": uint64, "depth_peak_index": uint64}, n+1 rows each:
+        the largest D2 of the label, the sum over its voxels, and the linear index of the voxel that holds the largest, the first
+        in raster order on a tie.  Row 0 and a label without a voxel read 0, 0 and 2^64 - 1.  return_map: the dict also holds
+        "depth_map", the D2 volume in HBM (int32 tensor, uint32 payload).  Needs two more volumes of the labels' size while it
+        runs; the one that is not returned is freed."""
+        torch = self.torch
+        Z, Y, X = self._label_volume("cc_depth", labels)
+        spacing = tuple(spacing) if isinstance(spacing, (tuple, list)) else (spacing,)
+        if len(spacing) != 3 or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= 64 for w in spacing):
+            raise ValueError(f"cc_depth: spacing = {spacing!r}: expected three integers 1..64 (wz, wy, wx)")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"cc_depth: n = {n}")
+        work_a = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
+        work_b = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
+        out = {"depth_max_sq": np.zeros(n + 1, dtype=np.uint32), "depth_sum_sq": np.zeros(n + 1, dtype=np.uint64),
+               "depth_peak_index": np.zeros(n + 1, dtype=np.uint64)}
+        self._enter()
+        try:
+            self._check(self.lib.dlv_cc_depth_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n, *(int(w) for w in spacing),
+                                                  C.c_void_p(work_a.data_ptr()), C.c_void_p(work_b.data_ptr()),
+                                                  *(a.ctypes.data_as(C.c_void_p) for a in out.values())))
+        finally:
+            self._leave()
+        if return_map:
+            out["depth_map"] = work_a
+        return out
+
     def cc_split(self, labels, n: int, depth: int, min_core: int = 1):
         """Fused cells split by their erosion cores, in place (dlv_cc_split_dev).  labels: int32 (uint32 payload) (Z,Y,X) in HBM,
         contiguous, labels 0..n.  The labels are eroded `depth` (1..16) times with the 6 face neighbours; what is left are the

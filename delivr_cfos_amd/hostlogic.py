@@ -588,6 +588,84 @@ def cell_shape_csv_text(stats: dict, n: int) -> str:
     return "\n".join(lines) + "\n"
 
 
+DEPTH_RAW_KEYS = ("depth_max_sq", "depth_sum_sq", "depth_peak_index")  # what HipEngine.cc_depth returns
+DEPTH_KEYS = DEPTH_RAW_KEYS + ("depth_radius", "depth_mean_sq", "depth_peak", "depth_spacing")  # finish_depth's keys
+DEPTH_NO_PEAK = 2**64 - 1  # depth_peak_index of a label without a voxel
+DEPTH_MAX_SPACING = 64  # dlv_cc_depth_dev's largest spacing
+_DEPTH_RAW_DTYPES = (np.uint32, np.uint64, np.uint64)
+
+
+def depth_stats_settings(settings):
+    """count_blobs' per-cell depth: None when settings["mi355x"]["depth_stats"] is absent or false, else the voxel spacing
+    (wz, wy, wx) of the distance map: settings["mi355x"]["depth_spacing"], three integers 1..64 (default [1, 1, 1]).  ValueError for
+    a depth_stats that is not a bool, for a spacing that is anything else (a bool, a float, two values, a value outside the range)
+    and for depth_spacing without depth_stats."""
+    mi = (settings or {}).get("mi355x") or {}
+    value, spacing = mi.get("depth_stats"), mi.get("depth_spacing")
+    if value is not None and value is not True and value is not False:
+        raise ValueError(f"settings['mi355x']['depth_stats'] = {value!r}: expected true or false")
+    if spacing is not None:
+        if (not isinstance(spacing, (list, tuple)) or len(spacing) != 3
+                or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= DEPTH_MAX_SPACING for w in spacing)):
+            raise ValueError(f"settings['mi355x']['depth_spacing'] = {spacing!r}: expected the voxel spacing [wz, wy, wx], three "
+                             f"integers 1..{DEPTH_MAX_SPACING}")
+    if not value:
+        if spacing is not None:
+            raise ValueError(f"settings['mi355x']['depth_spacing'] = {spacing!r} needs settings['mi355x']['depth_stats']: it is the "
+                             "voxel spacing of the depth map")
+        return None
+    return (1, 1, 1) if spacing is None else tuple(int(w) for w in spacing)
+
+
+def finish_depth(raw: dict, voxel_counts, shape, spacing) -> dict:
+    """HipEngine.cc_depth's arrays of a volume of `shape` (Z, Y, X), measured with `spacing` (wz, wy, wx) -> what count_blobs stores,
+    N+1 rows each, row 0 zero: depth_max_sq uint32, depth_sum_sq uint64 and depth_peak_index uint64, the exact integers (the
+    squared distances are in spacing units); depth_radius float64 = sqrt(depth_max_sq), the radius of the largest ball inscribed in
+    the cell, one rounding; depth_mean_sq float64 = depth_sum_sq / voxel_count; depth_peak int64 (N+1, 3), the z, y, x of the
+    deepest voxel - always a voxel of the cell, the first in raster order on a tie; depth_spacing, the tuple.  A label without a
+    voxel has zeros everywhere.  RuntimeError for rows that do not match the voxel counts, for a label 1..N with voxels but no peak
+    (or a peak without voxels) and for a peak outside the volume: labels and statistics do not belong together."""
+    counts = np.asarray(voxel_counts)
+    mx, sm, idx = (np.array(raw[k], dtype=dt) for k, dt in zip(DEPTH_RAW_KEYS, _DEPTH_RAW_DTYPES))
+    Z, Y, X = (int(v) for v in shape)
+    rows = len(mx)
+    if rows < 1 or len(counts) != rows or mx.shape != (rows,) or sm.shape != (rows,) or idx.shape != (rows,):
+        raise RuntimeError(f"depth statistics of {rows} rows beside voxel counts of {len(counts)}")
+    present = idx != np.uint64(DEPTH_NO_PEAK)
+    present[0] = False
+    bad = np.flatnonzero(present[1:] != (counts[1:] != 0)) + 1
+    if len(bad):
+        l = int(bad[0])
+        raise RuntimeError(f"depth statistics and voxel counts disagree on {len(bad)} label(s), first label {l}: "
+                           f"{int(counts[l])} voxels counted, {'a' if present[l] else 'no'} deepest voxel measured - labels and "
+                           "statistics of different brains?")
+    if present.any() and int(idx[present].max()) >= Z * Y * X:
+        raise RuntimeError(f"a depth peak at index {int(idx[present].max())} outside the volume of shape {(Z, Y, X)}")
+    mx[~present] = 0
+    sm[~present] = 0
+    idx[~present] = 0
+    radius = np.sqrt(mx.astype(np.float64))
+    mean = np.zeros(rows, dtype=np.float64)
+    np.divide(sm.astype(np.float64), counts.astype(np.float64), out=mean, where=present)
+    peak = np.stack(np.unravel_index(idx.astype(np.int64), (Z, Y, X)), axis=1).astype(np.int64)
+    return {"depth_max_sq": mx, "depth_sum_sq": sm, "depth_peak_index": idx, "depth_radius": radius, "depth_mean_sq": mean,
+            "depth_peak": peak, "depth_spacing": tuple(int(w) for w in spacing)}
+
+
+def cell_depth_csv_text(stats: dict, n: int) -> str:
+    """count_blobs' cell_depth/<brain>.csv: header ``Blob,Size,Radius,MeanSqDepth,PeakZ,PeakY,PeakX``, one row per label 1..N - all
+    N, as cell_intensity_csv_text - integers written plainly, floats as repr of the float64 value, every line ended by a newline."""
+    n = int(n)
+    counts = np.asarray(stats["voxel_counts"])[1:n + 1].tolist()
+    floats = [np.asarray(stats[k], dtype=np.float64)[1:n + 1].tolist() for k in ("depth_radius", "depth_mean_sq")]
+    peak = np.asarray(stats["depth_peak"], dtype=np.int64)[1:n + 1].tolist()
+    if any(len(c) != n for c in [counts, peak] + floats):
+        raise ValueError("statistics shorter than the label count")
+    lines = ["Blob,Size,Radius,MeanSqDepth,PeakZ,PeakY,PeakX"]
+    lines.extend(f"{i},{c},{r!r},{m!r},{z},{y},{x}" for i, (c, r, m, (z, y, x)) in enumerate(zip(counts, *floats, peak), 1))
+    return "\n".join(lines) + "\n"
+
+
 def fill_holes_enabled(settings) -> bool:
     """count_blobs' hole filling of the cell mask: False when settings["mi355x"]["fill_holes"] is absent or false, True when it is
     true.  ValueError for anything but a bool."""
@@ -642,7 +720,8 @@ class CountOptions:
     split: Optional[Tuple[int, int]] = None  # split_fused_settings
     label_file: str = "dense"  # label_file_format
     confidence: bool = False  # confidence_stats_enabled
-    fill_holes: bool = False  # fill_holes_enabled
+    depth: Optional[Tuple[int, int, int]] = None  # depth_stats_settings
+    fill_holes: bool = False  # fill_holes_enabled (the last field: tests/test_fill_holes_cpu.py pins it)
 
     @property
     def runs_file(self) -> bool:
@@ -670,9 +749,10 @@ def count_options(settings, min_size, max_size) -> CountOptions:
     shape = shape_stats_enabled(settings)
     confidence = confidence_stats_enabled(settings)
     fill = fill_holes_enabled(settings)
+    depth = depth_stats_settings(settings)
     return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
                         shape=shape, split=split, label_file=label_file_format(settings), confidence=confidence,
-                        fill_holes=fill)
+                        fill_holes=fill, depth=depth)
 
 
 INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
@@ -681,27 +761,36 @@ SHELL_QUARTILE_STATS_KEYS = SHELL_QUARTILE_KEYS + ("shell_radius",)  # ... and b
 RAW_GROUPS = frozenset(("cells", "shell", "cell_quartiles", "shell_quartiles"))  # the groups of measuring_plan taken from the raw volume
 
 
+def _same_setting(stored, asked) -> bool:
+    """a setting recorded in the pickle (an int, or a sequence of ints) is the one asked for"""
+    if isinstance(asked, tuple):
+        return isinstance(stored, (tuple, list, np.ndarray)) and tuple(int(v) for v in stored) == asked
+    return stored == asked
+
+
 def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     """The groups of per-cell statistics count_blobs has to measure: those `opts` asks for and `stats` - the cached pickle, None
     without one - does not hold completely.  A group is complete with every key of its row; a row that lists shell_radius also needs
-    the radius asked for (shells of another radius are other shells)."""
+    the radius asked for (shells of another radius are other shells), and one that lists depth_spacing the spacing asked for."""
     shell = opts.shell_radius > 0
+    settings_keys = {"shell_radius": opts.shell_radius, "depth_spacing": opts.depth}  # the keys that record how a row was measured
     rows = (("cells", opts.intensity, INTENSITY_STATS_KEYS),
             ("shell", opts.intensity and shell, SHELL_STATS_KEYS),
             ("cell_quartiles", opts.quartiles, QUARTILE_KEYS),
             ("shell_quartiles", opts.quartiles and shell, SHELL_QUARTILE_STATS_KEYS),
             ("shape", opts.shape, SHAPE_KEYS),
-            ("confidence", opts.confidence, CONFIDENCE_KEYS))
+            ("confidence", opts.confidence, CONFIDENCE_KEYS),
+            ("depth", opts.depth is not None, DEPTH_KEYS))
 
     def complete(keys) -> bool:
         return (stats is not None and all(k in stats for k in keys)
-                and ("shell_radius" not in keys or stats["shell_radius"] == opts.shell_radius))
+                and all(k not in keys or _same_setting(stats[k], asked) for k, asked in settings_keys.items()))
 
     return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
 
 
-_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "split_fused", "size_filter", "label_file")
-_HBM_CACHED = ("label_file", "shape_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
+_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "depth_stats", "split_fused", "size_filter", "label_file")
+_HBM_CACHED = ("label_file", "shape_stats", "depth_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
 
 
 def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxels: int, budget: int, runs_decoded: bool = False) -> None:
@@ -725,6 +814,7 @@ def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxe
                                 f"up to 2 more bytes per voxel in HBM beside {resident}, the raw volume{' and the shell' if s else ''}", None),
         "confidence_stats": ("confidence" in measured, "", 4, f"the probabilities (4 more bytes per voxel) in HBM beside {resident}", "measure"),
         "shape_stats": ("shape" in measured, "", 0, f"{resident} in HBM", "measure"),
+        "depth_stats": ("depth" in measured, "", 8, f"8 more bytes per voxel in HBM beside {resident}", "measure"),
         "split_fused": (opts.split is not None, f" = {opts.split and opts.split[0]}", 8,
                         f"8 more bytes per voxel in HBM beside {resident}", "split"),
         "size_filter": (opts.filter_active, "", 0, f"{resident} in HBM", "filter"),

@@ -358,6 +358,24 @@ int dlv_cc_shell_dev(dlv_ctx* ctx, const uint32_t* labels_dev, const uint16_t* r
  * DLV_EUNSUP (as dlv_cc_stats_dev). Synchronous. */
 int dlv_cc_shape_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Zb, int Y, int X, int z_first, int nz, int z_abs0, uint64_t n,
                      uint32_t* counts, uint64_t* sums, uint64_t* moments, uint64_t* faces, uint32_t* surface_voxels);
+/* Per-label depth from the exact label-wise Euclidean distance map (no counterpart in the reference, whose users call
+ * scipy.ndimage.distance_transform_edt per cell on the host; csrc/cc_depth.hip). labels_dev: uint32 (Z,Y,X) contiguous, labels 0..n,
+ * not modified; wz, wy, wx: the voxel spacings, integers 1..64. For a voxel v with 1 <= labels(v) <= n
+ *   D2(v) = min over u with labels(u) != labels(v) of (wz (vz - uz))^2 + (wy (vy - uy))^2 + (wx (vx - ux))^2,
+ * where every position outside the volume counts as background: a cell cut by a face of the volume is shallow there and D2 is always
+ * finite. D2(v) = 0 where labels(v) is 0 or above n; a label above n still differs from every label as a neighbour (as in
+ * dlv_cc_shape_dev), and a touching cell of another label bounds a cell exactly as the background does. Integer work only: exact
+ * and independent of scheduling. work_a_dev, work_b_dev: two scratch volumes of Z*Y*X uint32; on return work_a_dev holds D2 of every
+ * voxel of the volume, fully written, and work_b_dev is undefined. Host outputs of n+1 rows: max_d2 uint32 = the largest D2 of the
+ * label, sum_d2 uint64 = the exact sum of D2 over its voxels, peak_index uint64 = the linear index (z*Y + y)*X + x of the voxel with
+ * the largest D2, the first in C-raster order on a tie. Row 0 (the background is not measured) and a label without a voxel read 0,
+ * 0 and 2^64 - 1. DLV_EINVAL before any launch for a NULL pointer, Z/Y/X < 1, a spacing outside 1..64, n >= 2^32 - 1, a pointer
+ * that is not 4-byte aligned or any two of the three volumes overlapping. DLV_EUNSUP before any launch, with a message that names
+ * the axis, where w_a * ceil((dim_a + 1) / 2) >= 65536 on an axis a (below that every intermediate fits uint32), and for a volume
+ * above 2^32 voxels (the peak's index has 32 bits; the kernels take whole rows, so the launch grid sets no bound of its own).
+ * Synchronous. */
+int dlv_cc_depth_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                     uint32_t* work_a_dev, uint32_t* work_b_dev, uint32_t* max_d2, uint64_t* sum_d2, uint64_t* peak_index);
 /* Fused cells split by their erosion cores (no counterpart in the reference). labels_dev: uint32 (Z,Y,X) contiguous, labels 0..n,
  * rewritten in place. (1) Cores: C_0 = labels != 0; C_{k+1}(v) = C_k(v) and C_k(u) for the 6 face neighbours u of v, a neighbour
  * outside the volume counting as background; C = C_depth. (2) The cores are labelled 1..M as dlv_ccl26_dev labels a mask; with

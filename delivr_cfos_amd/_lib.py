@@ -241,6 +241,8 @@ SIGNATURES = {
     "dlv_cc_depth_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "dlv_cc_split_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int64, _P, _P, C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), _P, C.c_uint64]),
+    "dlv_cc_split_depth_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int,
+                                         C.c_int64, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, C.c_uint64]),
     "dlv_cc_runs_count_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_uint64)]),
     "dlv_cc_runs_emit_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "dlv_cc_runs_decode_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, _P, _P, C.c_uint64, _P]),

@@ -100,6 +100,15 @@ def _note_split(split, n_before: int, n_after: int, components_split: int):
           f"{n_after} cells")
 
 
+def _note_split_depth(split_depth, radius, n_before: int, n_after: int, components_split: int):
+    core_d2, fraction, min_core, spacing = split_depth
+    count_blobs.last_split = {"core_d2": int(core_d2), "fraction": int(fraction), "spacing": tuple(int(w) for w in spacing),
+                              "min_core": int(min_core), "n_before": int(n_before), "n_after": int(n_after),
+                              "components_split": int(components_split)}
+    print(f"split of fused cells (radius {radius}: core_d2 {core_d2}, fraction {fraction} %, spacing {list(spacing)}, min_core {min_core}): "
+          f"{components_split} of {n_before} components split, {n_after} cells")
+
+
 def _note_fill(voxels_filled: int, holes: int, n_after: int):
     # (the components before the fill are not named: the cells a cavity swallowed are only known from a second labelling)
     count_blobs.last_fill = {"holes": int(holes), "voxels_filled": int(voxels_filled), "n_after": int(n_after)}
@@ -475,6 +484,20 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     ValueError on every rank: the growth has no bounded reach, so a slab cannot be split on its own.  Off, 0 or absent: nothing of
     this happens.
 
+    ``settings["mi355x"]["split_radius"]`` = r and / or ``settings["mi355x"]["split_fraction"]`` = p (``depth_spacing`` = [wz, wy, wx],
+    default [1, 1, 1]; ``split_min_core`` as above): the same split with other cores, for stacks whose voxels are not cubes - one
+    erosion step of split_fused takes 6 um along z and 1.6 um along y and x off the reference's voxels, and a nucleus of two planes
+    is gone after the first.  The cores are the voxels that lie at least r - a number above 0 in the unit of depth_spacing, taken as
+    core_d2 = ceil(r * r) - from the outside of their cell, and at least p per cent (an integer 1..99) of their cell's inscribed
+    radius: the exact label-wise distance map of depth_stats, thresholded per cell (HipEngine.cc_split_depth).  With p every cell
+    has a core; a cell thinner than r has none and stays whole.  Growth, numbering, the place in the order, split_parent and
+    split_siblings, the cached labelling that is NOT split again, the 8 bytes of HBM per voxel and the refusals - slab-streamed
+    mask: MemoryError; torch.distributed: ValueError on every rank - are those of split_fused, and the two are alternatives: both
+    at once is a ValueError.  The pickle gains split_core_d2, split_fraction and split_spacing (and no split_depth: that is the
+    erosion depth), and ``count_blobs.last_split`` holds {"core_d2", "fraction", "spacing", "min_core", "n_before", "n_after",
+    "components_split"}.  depth_stats in the same run shares the spacing and is measured after the split, on the final labels.
+    Absent: nothing of this happens, and no new kernel is launched.
+
     ``settings["mi355x"]["label_file"]`` = "runs": the final labels - after the split and the size filter - are run-length coded on
     the device (HipEngine.cc_runs_encode) and written as <brain>-<N>-cc3d.runs (label_runs.py: the format, and load_labels for the
     steps that read it) by the same side thread, under the same ``defer_write`` contract; NO dense .npy file is written and the label
@@ -534,7 +557,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     count_blobs.last_quartiles = None  # set by a run with settings["mi355x"]["intensity_quartiles"]
     count_blobs.last_intensity = None  # set by a run with settings["mi355x"]["intensity_stats"]
     count_blobs.last_shape = None  # set by a run with settings["mi355x"]["shape_stats"]
-    count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"])
+    count_blobs.last_split = None  # set by a run that split (settings["mi355x"]["split_fused"], or "split_radius" / "split_fraction")
     count_blobs.last_confidence = None  # set by a run with settings["mi355x"]["confidence_stats"]
     count_blobs.last_fill = None  # set by a run that filled holes (settings["mi355x"]["fill_holes"])
     count_blobs.last_depth = None  # set by a run with settings["mi355x"]["depth_stats"]
@@ -557,6 +580,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['split_fused'] = {split[0]} is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
                          "its own; run step 3 on one device or switch split_fused off")
+    if sharded and opts.split_depth is not None:
+        # (as for split_fused: all raise, before any collective, or none does)
+        raise ValueError(f"count_blobs: settings['mi355x']['split_radius'] / ['split_fraction'] is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): a core grows back through its whole component, so a Z-slab cannot be split on "
+                         "its own; run step 3 on one device or switch split_radius and split_fraction off")
     if sharded and opts.fill_holes:
         # (as for split_fused: all raise, before any collective, or none does)
         raise ValueError(f"count_blobs: settings['mi355x']['fill_holes'] is not available under torch.distributed "
@@ -762,6 +790,12 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                 N, split_parent, components_split = eng.cc_split(labels_dev, N, split[0], split[1])
                 _note_split(split, n_components, N, components_split)
                 mark("split")
+            elif opts.split_depth is not None:
+                n_components = N
+                core_d2, fraction, min_core, spacing = opts.split_depth
+                N, split_parent, components_split = eng.cc_split_depth(labels_dev, N, spacing, core_d2, fraction, min_core)
+                _note_split_depth(opts.split_depth, (settings.get("mi355x") or {}).get("split_radius"), n_components, N, components_split)
+                mark("split")
             if opts.filter_active:
                 n_before = N
                 counts_dev = eng.cc_counts(labels_dev, N)
@@ -818,6 +852,9 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                 print(f"size filter: the cached labelling is reused as it is, min_size {bounds[0]} / max_size {bounds[1]} are not applied to it")
             if split is not None:
                 print(f"split of fused cells: the cached labelling is reused as it is, it is not split (depth {split[0]}) again")
+            if opts.split_depth is not None:
+                print(f"split of fused cells: the cached labelling is reused as it is, it is not split (core_d2 {opts.split_depth[0]}, "
+                      f"fraction {opts.split_depth[1]} %) again")
             if opts.fill_holes:
                 print("fill of holes: the cached labelling is reused as it is, its holes are not filled")
             split_parent, hole_voxels, filled = None, None, None
@@ -863,7 +900,11 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                 stats = eng.cc_stats(labels_dev, N)
             if split_parent is not None:
                 stats.update(finish_split(split_parent, count_blobs.last_split["n_before"]))
-                stats["split_depth"] = int(split[0])
+                if split is not None:
+                    stats["split_depth"] = int(split[0])
+                else:
+                    stats["split_core_d2"], stats["split_fraction"] = int(opts.split_depth[0]), int(opts.split_depth[1])
+                    stats["split_spacing"] = tuple(int(w) for w in opts.split_depth[3])
             if hole_voxels is not None:
                 stats["hole_voxels"], stats["holes_filled"] = hole_voxels, int(filled[1])
             if not plan:

@@ -31,6 +31,19 @@ inline int check_tile_grid(dlv_ctx* ctx, const char* what, const dim3& grid, int
     return DLV_OK;
 }
 
+// a voxel spacing of the distance map (cc_depth.hip)
+inline int check_spacing(dlv_ctx* ctx, const char* what, const char* axis, int w) {
+    if (w < 1 || w > 64) return dlv_fail(ctx, DLV_EINVAL, "%s: spacing w%s = %d is outside 1..64", what, axis, w);
+    return DLV_OK;
+}
+// every (w d)^2 of a walk of the distance map, and so every value of the map, stays below 2^32
+inline int check_reach(dlv_ctx* ctx, const char* what, const char* axis, int w, int dim) {
+    if ((long long)w * (((long long)dim + 2) / 2) >= 65536)
+        return dlv_fail(ctx, DLV_EUNSUP, "%s: axis %s: spacing %d over %d voxels: %d * ceil((%d + 1) / 2) does not stay below 65536, "
+                        "the squared distances are uint32", what, axis, w, dim, w, dim);
+    return DLV_OK;
+}
+
 // [a, a + bytes) and [b, b + bytes) share a byte
 inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;

@@ -219,46 +219,16 @@ __global__ void __launch_bounds__(256) cc_depth_walk_kernel(const u32* __restric
     }
 }
 
-inline int check_spacing(dlv_ctx* ctx, const char* axis, int w) {
-    if (w < 1 || w > 64) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: spacing w%s = %d is outside 1..64", axis, w);
-    return DLV_OK;
-}
-// every (w d)^2 of a walk, and so every value of the map, stays below 2^32
-inline int check_reach(dlv_ctx* ctx, const char* axis, int w, int dim) {
-    if ((long long)w * (((long long)dim + 2) / 2) >= 65536)
-        return dlv_fail(ctx, DLV_EUNSUP, "cc_depth: axis %s: spacing %d over %d voxels: %d * ceil((%d + 1) / 2) does not stay below 65536, "
-                        "the squared distances are uint32", axis, w, dim, w, dim);
-    return DLV_OK;
-}
-
 }  // namespace
 
-extern "C" int dlv_cc_depth_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
-                                uint32_t* work_a_dev, uint32_t* work_b_dev, uint32_t* max_d2, uint64_t* sum_d2, uint64_t* peak_index) {
-    if (!ctx) return DLV_EINVAL;
-    if (!labels_dev || !work_a_dev || !work_b_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: labels_dev, work_a_dev or work_b_dev is NULL");
-    if (!max_d2 || !sum_d2 || !peak_index) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: max_d2, sum_d2 or peak_index is NULL");
-    DLV_TRY(check_volume(ctx, "cc_depth", Z, Y, X));
-    DLV_TRY(check_spacing(ctx, "z", wz));
-    DLV_TRY(check_spacing(ctx, "y", wy));
-    DLV_TRY(check_spacing(ctx, "x", wx));
-    DLV_TRY(check_label_count(ctx, "cc_depth", n));
-    if (((uintptr_t)labels_dev & 3) || ((uintptr_t)work_a_dev & 3) || ((uintptr_t)work_b_dev & 3))
-        return dlv_fail(ctx, DLV_EINVAL, "cc_depth: labels, work_a and work_b must be 4-byte aligned");
-    DLV_TRY(check_reach(ctx, "z", wz, Z));
-    DLV_TRY(check_reach(ctx, "y", wy, Y));
-    DLV_TRY(check_reach(ctx, "x", wx, X));
-    const u64 nvox = (u64)Z * Y * X;  // (each dimension is below 2^17 here: no wrap)
-    if (nvox > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "cc_depth: volumes above 2^32 voxels: the peak's index has 32 bits");
-    const size_t bytes = (size_t)nvox * 4;
-    if (ranges_overlap(work_a_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: work_a_dev overlaps labels_dev");
-    if (ranges_overlap(work_b_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: work_b_dev overlaps labels_dev");
-    if (ranges_overlap(work_b_dev, work_a_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: work_b_dev overlaps work_a_dev");
-    DLV_HIP(ctx, hipSetDevice(ctx->device));
+// the three passes for checked arguments (common.h): D2 into work_a, the keys and sums into the scratch slot; no read-back
+int dlv_cc_depth_passes(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                        uint32_t* work_a_dev, uint32_t* work_b_dev, size_t extra_bytes, DlvDepthTables* out) {
+    const u64 nvox = (u64)Z * Y * X;
     const size_t rows = (size_t)n + 1;
-    // device accumulators: [key u64 rows | sum u64 rows]; an absent label keeps zeros
+    // device accumulators: [key u64 rows | sum u64 rows | the caller's bytes]; an absent label keeps zeros
     WsCarve carve;
-    const size_t off_key = carve.take(rows * 8), off_sum = carve.take(rows * 8);
+    const size_t off_key = carve.take(rows * 8), off_sum = carve.take(rows * 8), off_extra = carve.take(extra_bytes);
     char* ws;
     DLV_TRY(dlv_ws_get(ctx, WS_MISC, carve.end, (void**)&ws));
     DLV_HIP(ctx, hipMemsetAsync(ws, 0, carve.end, ctx->stream));
@@ -287,9 +257,40 @@ extern "C" int dlv_cc_depth_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z,
         pr.end();
     }
     DLV_LAUNCH_CHECK(ctx, "cc_depth_walk_kernel (z)");
+    out->key = (uint64_t*)(ws + off_key);
+    out->sum = (uint64_t*)(ws + off_sum);
+    out->extra = ws + off_extra;
+    return DLV_OK;
+}
+
+extern "C" int dlv_cc_depth_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                                uint32_t* work_a_dev, uint32_t* work_b_dev, uint32_t* max_d2, uint64_t* sum_d2, uint64_t* peak_index) {
+    if (!ctx) return DLV_EINVAL;
+    if (!labels_dev || !work_a_dev || !work_b_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: labels_dev, work_a_dev or work_b_dev is NULL");
+    if (!max_d2 || !sum_d2 || !peak_index) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: max_d2, sum_d2 or peak_index is NULL");
+    DLV_TRY(check_volume(ctx, "cc_depth", Z, Y, X));
+    DLV_TRY(check_spacing(ctx, "cc_depth", "z", wz));
+    DLV_TRY(check_spacing(ctx, "cc_depth", "y", wy));
+    DLV_TRY(check_spacing(ctx, "cc_depth", "x", wx));
+    DLV_TRY(check_label_count(ctx, "cc_depth", n));
+    if (((uintptr_t)labels_dev & 3) || ((uintptr_t)work_a_dev & 3) || ((uintptr_t)work_b_dev & 3))
+        return dlv_fail(ctx, DLV_EINVAL, "cc_depth: labels, work_a and work_b must be 4-byte aligned");
+    DLV_TRY(check_reach(ctx, "cc_depth", "z", wz, Z));
+    DLV_TRY(check_reach(ctx, "cc_depth", "y", wy, Y));
+    DLV_TRY(check_reach(ctx, "cc_depth", "x", wx, X));
+    const u64 nvox = (u64)Z * Y * X;  // (each dimension is below 2^17 here: no wrap)
+    if (nvox > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "cc_depth: volumes above 2^32 voxels: the peak's index has 32 bits");
+    const size_t bytes = (size_t)nvox * 4;
+    if (ranges_overlap(work_a_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: work_a_dev overlaps labels_dev");
+    if (ranges_overlap(work_b_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: work_b_dev overlaps labels_dev");
+    if (ranges_overlap(work_b_dev, work_a_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_depth: work_b_dev overlaps work_a_dev");
+    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t rows = (size_t)n + 1;
+    DlvDepthTables t;
+    DLV_TRY(dlv_cc_depth_passes(ctx, labels_dev, Z, Y, X, n, wz, wy, wx, work_a_dev, work_b_dev, 0, &t));
     std::vector<u64> keys(rows);
-    DLV_HIP(ctx, hipMemcpyAsync(keys.data(), ws + off_key, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-    DLV_HIP(ctx, hipMemcpyAsync(sum_d2, ws + off_sum, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    DLV_HIP(ctx, hipMemcpyAsync(keys.data(), t.key, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    DLV_HIP(ctx, hipMemcpyAsync(sum_d2, t.sum, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t l = 0; l < rows; ++l) {  // (key 0: no voxel)
         max_d2[l] = (uint32_t)(keys[l] >> 32);

@@ -14,6 +14,12 @@
 // Only labels with two or more cores are grown: G_0 holds their cores alone, the voxels of every other label hold SKIP and are
 // never pending.  Integer work only; one writer per voxel in the sweeps, and the tables are written with atomicMin / atomicAdd
 // or by writers that agree: the result is exact and independent of scheduling.
+//
+// dlv_cc_split_depth_dev is the same split with other cores, for stacks whose voxels are not cubes (one erosion step takes a
+// whole plane off a cell that is two planes thick): C(v) = D2(v) >= T(L(v)), with D2 the exact label-wise distance map of
+// cc_depth.hip in integer spacings and T(l) = max(core_d2, ceil(core_pct^2 m(l) / 10000), 1) from the largest D2 of the label - a
+// Euclidean erosion in physical units.  D2 lies in work_a, the byte mask goes to work_b, and from Q on both entries run
+// split_from_cores.  The threshold cannot be folded into the z pass of the map: m(l) is known only when that pass has ended.
 #include "common.h"
 #include "cc_check.h"
 #include "cc_tile.h"  // (the tile of the growth)
@@ -51,6 +57,15 @@ __device__ __forceinline__ unsigned nz4(const u32* __restrict__ p, int valid) {
     return b;
 }
 
+// p[j] = bit j of c, for j < valid (<= 4): one 4-byte store where the four are whole and aligned
+__device__ __forceinline__ void store_mask4(uint8_t* __restrict__ p, int valid, unsigned c) {
+    if (valid == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+        *reinterpret_cast<u32*>(p) = (c & 1u) | ((c & 2u) << 7) | ((c & 4u) << 14) | ((c & 8u) << 21);
+    } else {
+        for (int j = 0; j < valid; ++j) p[j] = (uint8_t)((c >> j) & 1u);
+    }
+}
+
 // One erosion step: dst = C_{k+1} of src = C_k (a byte mask), or of the labels for the first step.  A thread takes four voxels
 // along x; the neighbour rows are read only where the four and their x neighbours left something (cells: < 1 % foreground).
 template <typename T>
@@ -74,12 +89,48 @@ __global__ void __launch_bounds__(256) split_erode_kernel(const T* __restrict__ 
             if (c) c &= z > 0 ? nz4(src + at - (u64)Y * X, valid) : 0u;
             if (c) c &= z + 1 < Z ? nz4(src + at + (u64)Y * X, valid) : 0u;
         }
-        uint8_t* p = dst + at;
-        if (valid == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
-            *reinterpret_cast<u32*>(p) = (c & 1u) | ((c & 2u) << 7) | ((c & 4u) << 14) | ((c & 8u) << 21);
+        store_mask4(dst + at, valid, c);
+    }
+}
+
+// T(l) of dlv_cc_split_depth_dev for the rows 0..n: key[l] >> 32 is m(l), the largest D2 of label l (cc_depth.hip's peak keys)
+__global__ void __launch_bounds__(256) split_depth_threshold_kernel(const u64* __restrict__ key, u64 N, u32 core_d2, u32 core_pct,
+                                                                    u32* __restrict__ T) {
+    for (u64 l = (u64)blockIdx.x * blockDim.x + threadIdx.x; l <= N; l += (u64)gridDim.x * blockDim.x) {
+        const u64 m = key[l] >> 32;
+        const u64 part = ((u64)core_pct * core_pct * m + 9999u) / 10000u;  // (< 2^14 * 2^32; <= m)
+        T[l] = (u32)max(max((u64)core_d2, part), (u64)1);
+    }
+}
+
+// The cores of dlv_cc_split_depth_dev: dst(v) = 1 where 1 <= L(v) <= n and D2(v) >= T(L(v)), else 0.  A thread takes four voxels
+// along x, as split_erode_kernel: one 16-byte load of the labels and one of the map where the four are whole and aligned, and T is
+// read only under a voxel the map measured (D2 != 0: a label 1..n; cells: < 1 % of the voxels).
+__global__ void __launch_bounds__(256) split_depth_cores_kernel(const u32* __restrict__ L, const u32* __restrict__ D2,
+                                                                const u32* __restrict__ T, u32 n, int Z, int Y, int X,
+                                                                uint8_t* __restrict__ dst) {
+    const int qx = (X + 3) / 4;
+    const u64 total = (u64)Z * Y * qx;
+    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (u64)gridDim.x * blockDim.x) {
+        const int x = (int)(t % (u64)qx) * 4;
+        const u64 at = (t / (u64)qx) * (u64)X + x;
+        const int valid = min(4, X - x);
+        u32 l[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
+        if (valid == 4 && ((reinterpret_cast<uintptr_t>(L + at) | reinterpret_cast<uintptr_t>(D2 + at)) & 15) == 0) {
+            const u32x4_t lq = *reinterpret_cast<const u32x4_t*>(L + at), dq = *reinterpret_cast<const u32x4_t*>(D2 + at);
+            l[0] = lq.x; l[1] = lq.y; l[2] = lq.z; l[3] = lq.w;
+            d[0] = dq.x; d[1] = dq.y; d[2] = dq.z; d[3] = dq.w;
         } else {
-            for (int j = 0; j < valid; ++j) p[j] = (uint8_t)((c >> j) & 1u);
+            for (int j = 0; j < valid; ++j) {
+                l[j] = L[at + j];
+                d[j] = D2[at + j];
+            }
         }
+        unsigned c = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (d[j] != 0 && l[j] >= 1 && l[j] <= n && d[j] >= T[l[j]]) c |= 1u << j;
+        store_mask4(dst + at, valid, c);
     }
 }
 
@@ -268,51 +319,42 @@ __global__ void __launch_bounds__(256) split_apply_kernel(u32* __restrict__ L, c
     }
 }
 
-}  // namespace
-
-extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int depth, int64_t min_core,
-                                uint32_t* work_a_dev, uint32_t* work_b_dev, uint64_t* n_out, uint64_t* n_split_out,
-                                uint32_t* parent_dev, uint64_t parent_cap) {
-    if (!ctx) return DLV_EINVAL;
-    if (!labels_dev || !work_a_dev || !work_b_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_split: labels_dev, work_a_dev or work_b_dev is NULL");
-    if (!n_out || !n_split_out || !parent_dev) return dlv_fail(ctx, DLV_EINVAL, "cc_split: n_out, n_split_out or parent_dev is NULL");
-    DLV_TRY(check_volume(ctx, "cc_split", Z, Y, X));
-    if (depth < 1 || depth > 16) return dlv_fail(ctx, DLV_EINVAL, "cc_split: depth %d is outside 1..16", depth);
-    if (min_core < 1) return dlv_fail(ctx, DLV_EINVAL, "cc_split: min_core %lld is below 1", (long long)min_core);
+// the checks the two entries share, in two parts with an entry's own checks between them: the pointers and the shape ...
+int split_check_pointers(dlv_ctx* ctx, const char* what, const uint32_t* labels_dev, int Z, int Y, int X, const uint32_t* work_a_dev,
+                         const uint32_t* work_b_dev, const uint64_t* n_out, const uint64_t* n_split_out, const uint32_t* parent_dev) {
+    if (!labels_dev || !work_a_dev || !work_b_dev) return dlv_fail(ctx, DLV_EINVAL, "%s: labels_dev, work_a_dev or work_b_dev is NULL", what);
+    if (!n_out || !n_split_out || !parent_dev) return dlv_fail(ctx, DLV_EINVAL, "%s: n_out, n_split_out or parent_dev is NULL", what);
+    return check_volume(ctx, what, Z, Y, X);
+}
+// ... and min_core, the alignment, the tile grid of the growth, the 32-bit indices and labels, the three volumes apart
+int split_check_volumes(dlv_ctx* ctx, const char* what, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int64_t min_core,
+                        const uint32_t* work_a_dev, const uint32_t* work_b_dev, const uint32_t* parent_dev) {
+    if (min_core < 1) return dlv_fail(ctx, DLV_EINVAL, "%s: min_core %lld is below 1", what, (long long)min_core);
     if (((uintptr_t)labels_dev & 3) || ((uintptr_t)work_a_dev & 3) || ((uintptr_t)work_b_dev & 3) || ((uintptr_t)parent_dev & 3))
-        return dlv_fail(ctx, DLV_EINVAL, "cc_split: labels, work_a, work_b and parent must be 4-byte aligned");
-    const dim3 grid = tile_grid(Z, Y, X);
-    DLV_TRY(check_tile_grid(ctx, "cc_split", grid, Z, Y, X));
+        return dlv_fail(ctx, DLV_EINVAL, "%s: labels, work_a, work_b and parent must be 4-byte aligned", what);
+    DLV_TRY(check_tile_grid(ctx, what, tile_grid(Z, Y, X), Z, Y, X));
     const u64 nvox = (u64)Z * Y * X;
-    if (nvox > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "cc_split: volumes above 2^32 voxels need 64-bit labels");
-    DLV_TRY(check_label_count(ctx, "cc_split", n));
+    if (nvox > ((u64)1 << 32)) return dlv_fail(ctx, DLV_EUNSUP, "%s: volumes above 2^32 voxels need 64-bit labels", what);
+    DLV_TRY(check_label_count(ctx, what, n));
     const size_t bytes = (size_t)nvox * 4;
-    if (ranges_overlap(work_a_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_a_dev overlaps labels_dev");
-    if (ranges_overlap(work_b_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_b_dev overlaps labels_dev");
-    if (ranges_overlap(work_b_dev, work_a_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "cc_split: work_b_dev overlaps work_a_dev");
-    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    if (ranges_overlap(work_a_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "%s: work_a_dev overlaps labels_dev", what);
+    if (ranges_overlap(work_b_dev, labels_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "%s: work_b_dev overlaps labels_dev", what);
+    if (ranges_overlap(work_b_dev, work_a_dev, bytes)) return dlv_fail(ctx, DLV_EINVAL, "%s: work_b_dev overlaps work_a_dev", what);
+    return DLV_OK;
+}
+
+// Steps (2) - (4) of the two entries, for checked arguments: `core_mask` is the byte mask C of the cores, somewhere in work_b_dev;
+// work_a_dev holds nothing that is still needed.  Synchronous.
+int split_from_cores(dlv_ctx* ctx, const char* what, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int64_t min_core,
+                     const uint8_t* core_mask, uint32_t* work_a_dev, uint32_t* work_b_dev, uint64_t* n_out, uint64_t* n_split_out,
+                     uint32_t* parent_dev, uint64_t parent_cap) {
+    const dim3 grid = tile_grid(Z, Y, X);
+    const u64 nvox = (u64)Z * Y * X;
     const int flat = (int)std::min<u64>((nvox + 255) / 256, (u64)256 * 64);  // the grid-stride kernels over the voxels
     auto rows_grid = [](u64 rows) { return dim3((unsigned)std::min<u64>(std::max<u64>((rows + 255) / 256, 1), (u64)256 * 32)); };
-    DlvProf pr(ctx, "cc_split", 0.0, 0.0);
-
-    // (1) the cores: `depth` erosion steps between two byte masks that live in work_b until the cores are labelled
-    uint8_t* mask[2] = {(uint8_t*)work_b_dev, (uint8_t*)work_b_dev + (nvox >= 16 ? (nvox + 15) / 16 * 16 : nvox)};
-    {
-        DlvProf p1(ctx, "cc_split_erode", 0.0, (double)nvox * (5.0 + 2.0 * (depth - 1)));
-        const int ge = (int)std::min<u64>(((u64)Z * Y * ((X + 3) / 4) + 255) / 256, (u64)256 * 64);
-        for (int i = 1; i <= depth; ++i) {
-            if (i == 1)
-                hipLaunchKernelGGL(split_erode_kernel<u32>, dim3(ge), dim3(256), 0, ctx->stream, (const u32*)labels_dev, Z, Y, X, mask[1]);
-            else
-                hipLaunchKernelGGL(split_erode_kernel<uint8_t>, dim3(ge), dim3(256), 0, ctx->stream, (const uint8_t*)mask[(i - 1) & 1], Z, Y, X,
-                                   mask[i & 1]);
-        }
-        p1.end();
-        DLV_LAUNCH_CHECK(ctx, "split_erode_kernel");
-    }
-    // (2) their labels Q in work_a, 1..M
+    // (2) the labels Q of the cores in work_a, 1..M
     uint64_t M = 0;
-    DLV_TRY(dlv_ccl26_dev(ctx, mask[depth & 1], Z, Y, X, work_a_dev, &M));
+    DLV_TRY(dlv_ccl26_dev(ctx, core_mask, Z, Y, X, work_a_dev, &M));
     if (min_core > 1 && M > 0) {
         u32* sizes;  // (the labelling has returned: its scratch slot is free, and the filter does not touch it)
         DLV_TRY(dlv_ws_get(ctx, WS_CCL, ((size_t)M + 1) * 4, (void**)&sizes));
@@ -320,7 +362,7 @@ extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y
         DLV_TRY(dlv_cc_size_filter_dev(ctx, work_a_dev, nvox, M, sizes, min_core, -1, &M));
     }
     if (M + n >= 0xffffffffull)
-        return dlv_fail(ctx, DLV_EINVAL, "cc_split: %llu cores and n = %llu do not fit the uint32 keys", (unsigned long long)M, (unsigned long long)n);
+        return dlv_fail(ctx, DLV_EINVAL, "%s: %llu cores and n = %llu do not fit the uint32 keys", what, (unsigned long long)M, (unsigned long long)n);
 
     // tables: comp (M + 1), cores (n + 1), first (M + n + 1), the tile states, the change flags of a batch, two words
     // (the labels that are split, "a label above n")
@@ -347,7 +389,7 @@ extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y
     u32 host_word[2] = {0, 0};
     DLV_HIP(ctx, hipMemcpyAsync(host_word, word, 8, hipMemcpyDeviceToHost, ctx->stream));
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (host_word[1]) return dlv_fail(ctx, DLV_EINVAL, "cc_split: the volume holds a label above n = %llu", (unsigned long long)n);
+    if (host_word[1]) return dlv_fail(ctx, DLV_EINVAL, "%s: the volume holds a label above n = %llu", what, (unsigned long long)n);
 
     // (3) the growth, only with something to split: a step reads one buffer and writes the other; the flags of BATCH steps are
     // read back together, and the loop ends with the first step that assigned nothing - from that step on a step changes
@@ -388,13 +430,87 @@ extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y
     *n_out = K;
     *n_split_out = host_word[0];
     if (parent_cap < K + 1)
-        return dlv_fail(ctx, DLV_EINVAL, "cc_split: parent_dev of %llu rows does not hold the %llu pieces and row 0", (unsigned long long)parent_cap,
+        return dlv_fail(ctx, DLV_EINVAL, "%s: parent_dev of %llu rows does not hold the %llu pieces and row 0", what, (unsigned long long)parent_cap,
                         (unsigned long long)K);
     DLV_HIP(ctx, hipMemsetAsync(parent_dev, 0, ((size_t)K + 1) * 4, ctx->stream));
     hipLaunchKernelGGL(split_apply_kernel, dim3(flat), dim3(256), 0, ctx->stream, labels_dev, (const u32*)pieces, nvox, X, parent_dev);
     DLV_LAUNCH_CHECK(ctx, "split_apply_kernel");
     p4.end();
-    pr.end();
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DLV_OK;
+}
+
+}  // namespace
+
+extern "C" int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int depth, int64_t min_core,
+                                uint32_t* work_a_dev, uint32_t* work_b_dev, uint64_t* n_out, uint64_t* n_split_out,
+                                uint32_t* parent_dev, uint64_t parent_cap) {
+    if (!ctx) return DLV_EINVAL;
+    DLV_TRY(split_check_pointers(ctx, "cc_split", labels_dev, Z, Y, X, work_a_dev, work_b_dev, n_out, n_split_out, parent_dev));
+    if (depth < 1 || depth > 16) return dlv_fail(ctx, DLV_EINVAL, "cc_split: depth %d is outside 1..16", depth);
+    DLV_TRY(split_check_volumes(ctx, "cc_split", labels_dev, Z, Y, X, n, min_core, work_a_dev, work_b_dev, parent_dev));
+    const u64 nvox = (u64)Z * Y * X;
+    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    DlvProf pr(ctx, "cc_split", 0.0, 0.0);
+
+    // (1) the cores: `depth` erosion steps between two byte masks that live in work_b until the cores are labelled
+    uint8_t* mask[2] = {(uint8_t*)work_b_dev, (uint8_t*)work_b_dev + (nvox >= 16 ? (nvox + 15) / 16 * 16 : nvox)};
+    {
+        DlvProf p1(ctx, "cc_split_erode", 0.0, (double)nvox * (5.0 + 2.0 * (depth - 1)));
+        const int ge = (int)std::min<u64>(((u64)Z * Y * ((X + 3) / 4) + 255) / 256, (u64)256 * 64);
+        for (int i = 1; i <= depth; ++i) {
+            if (i == 1)
+                hipLaunchKernelGGL(split_erode_kernel<u32>, dim3(ge), dim3(256), 0, ctx->stream, (const u32*)labels_dev, Z, Y, X, mask[1]);
+            else
+                hipLaunchKernelGGL(split_erode_kernel<uint8_t>, dim3(ge), dim3(256), 0, ctx->stream, (const uint8_t*)mask[(i - 1) & 1], Z, Y, X,
+                                   mask[i & 1]);
+        }
+        p1.end();
+        DLV_LAUNCH_CHECK(ctx, "split_erode_kernel");
+    }
+    DLV_TRY(split_from_cores(ctx, "cc_split", labels_dev, Z, Y, X, n, min_core, mask[depth & 1], work_a_dev, work_b_dev, n_out, n_split_out,
+                             parent_dev, parent_cap));
+    pr.end();
+    return DLV_OK;
+}
+
+extern "C" int dlv_cc_split_depth_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                                      uint32_t core_d2, int core_pct, int64_t min_core, uint32_t* work_a_dev, uint32_t* work_b_dev,
+                                      uint64_t* n_out, uint64_t* n_split_out, uint32_t* parent_dev, uint64_t parent_cap) {
+    const char* what = "cc_split_depth";
+    if (!ctx) return DLV_EINVAL;
+    DLV_TRY(split_check_pointers(ctx, what, labels_dev, Z, Y, X, work_a_dev, work_b_dev, n_out, n_split_out, parent_dev));
+    DLV_TRY(check_spacing(ctx, what, "z", wz));
+    DLV_TRY(check_spacing(ctx, what, "y", wy));
+    DLV_TRY(check_spacing(ctx, what, "x", wx));
+    if (core_pct < 0 || core_pct > 99) return dlv_fail(ctx, DLV_EINVAL, "%s: core_pct %d is outside 0..99", what, core_pct);
+    if (core_d2 == 0 && core_pct == 0) return dlv_fail(ctx, DLV_EINVAL, "%s: core_d2 and core_pct are both 0: no core is defined", what);
+    DLV_TRY(check_reach(ctx, what, "z", wz, Z));  // (each dimension is below 2^17 from here on: no wrap of Z * Y * X)
+    DLV_TRY(check_reach(ctx, what, "y", wy, Y));
+    DLV_TRY(check_reach(ctx, what, "x", wx, X));
+    DLV_TRY(split_check_volumes(ctx, what, labels_dev, Z, Y, X, n, min_core, work_a_dev, work_b_dev, parent_dev));
+    const u64 nvox = (u64)Z * Y * X;
+    DLV_HIP(ctx, hipSetDevice(ctx->device));
+    DlvProf pr(ctx, "cc_split_depth", 0.0, 0.0);
+
+    // (1) D2 in work_a and the peak keys of the labels; (2) T(l) from the keys, then the cores as a byte mask at the start of
+    // work_b: work_b's values of the y pass are dead since the z pass, and D2 is dead once this kernel has read it
+    DlvDepthTables t;
+    DLV_TRY(dlv_cc_depth_passes(ctx, labels_dev, Z, Y, X, n, wz, wy, wx, work_a_dev, work_b_dev, ((size_t)n + 1) * 4, &t));
+    {
+        DlvProf p2(ctx, "cc_split_depth_cores", 0.0, (double)nvox * 9.0);
+        const int gt = (int)std::min<u64>((n + 1 + 255) / 256, (u64)256 * 32);
+        const int gc = (int)std::min<u64>(((u64)Z * Y * ((X + 3) / 4) + 255) / 256, (u64)256 * 64);
+        hipLaunchKernelGGL(split_depth_threshold_kernel, dim3(gt), dim3(256), 0, ctx->stream, (const u64*)t.key, (u64)n, (u32)core_d2,
+                           (u32)core_pct, (u32*)t.extra);
+        hipLaunchKernelGGL(split_depth_cores_kernel, dim3(gc), dim3(256), 0, ctx->stream, (const u32*)labels_dev, (const u32*)work_a_dev,
+                           (const u32*)t.extra, (u32)n, Z, Y, X, (uint8_t*)work_b_dev);
+        p2.end();
+        DLV_LAUNCH_CHECK(ctx, "split_depth_cores_kernel");
+    }
+    // (the tables of the distance map are read by launches queued before split_from_cores asks for their scratch slot again)
+    DLV_TRY(split_from_cores(ctx, what, labels_dev, Z, Y, X, n, min_core, (const uint8_t*)work_b_dev, work_a_dev, work_b_dev, n_out,
+                             n_split_out, parent_dev, parent_cap));
+    pr.end();
     return DLV_OK;
 }

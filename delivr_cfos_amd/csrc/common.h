@@ -276,6 +276,19 @@ size_t dlv_bf16_pack_bytes(const int features[6]);
 // forest_dev becomes the label volume: 1..N in the raster order of those first voxels, 0 where fg_dev is 0.  fg_dev is not
 // modified and must not be forest_dev; n <= 2^32 voxels; uses the labelling's scratch slot.  Synchronous (*n_out = N).
 int dlv_ccl_number_forest(dlv_ctx* ctx, const uint32_t* fg_dev, uint32_t* forest_dev, uint64_t n, uint64_t* n_out);
+// cc_depth.hip: the three passes of dlv_cc_depth_dev for a caller that has checked the arguments as that entry does (volume,
+// spacings, n, alignment, reach, 2^32 voxels, overlap) - dlv_cc_depth_dev itself and dlv_cc_split_depth_dev (cc_split.hip).  On
+// return the launches are queued on the context's stream: work_a_dev will hold D2 of every voxel, and the context's WS_MISC slot
+// the per-label tables of n + 1 rows each - key[l] = (the largest D2 of label l << 32) | (2^32 - 1 - the index of the first voxel
+// that holds it), 0 for a label without a voxel, and sum[l] = the sum of D2 - followed by `extra_bytes` for the caller, zeroed
+// like the tables.  The pointers hold until the slot is asked for again.  Asynchronous.
+struct DlvDepthTables {
+    uint64_t* key = nullptr;
+    uint64_t* sum = nullptr;
+    void* extra = nullptr;
+};
+int dlv_cc_depth_passes(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                        uint32_t* work_a_dev, uint32_t* work_b_dev, size_t extra_bytes, DlvDepthTables* out);
 #if defined(__HIPCC__)
 // Sum of a value over the 32 lanes of each wave half (lanes 0-31, lanes 32-63) with DPP adds only (five VALU
 // instructions, no LDS permute): the total is valid in lanes 16-31 resp. 48-63 - read it from lane 31 / 63.

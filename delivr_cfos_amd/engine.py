@@ -937,7 +937,6 @@ class HipEngine:
         The pieces and the labels that stay whole are renumbered 1..K in raster order of their first voxel, as ccl26 numbers.
         -> (K, parent: uint32 ndarray of K+1 with parent[j] = the old label of piece j and parent[0] = 0, the number of labels
         that were split).  Needs two more volumes of the labels' size while it runs."""
-        torch = self.torch
         Z, Y, X = self._label_volume("cc_split", labels)
         if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= 16:
             raise ValueError(f"cc_split: depth = {depth!r}: expected an integer 1..16")
@@ -946,8 +945,16 @@ class HipEngine:
         n = int(n)
         if n < 0:
             raise ValueError(f"cc_split: n = {n}")
-        work_a = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
-        work_b = torch.empty((Z, Y, X), dtype=torch.int32, device=self.device)
+        return self._split_call(labels, n, lambda *tail: self.lib.dlv_cc_split_dev(
+            self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n, int(depth), int(min_core), *tail))
+
+    def _split_call(self, labels, n: int, entry):
+        """The call of cc_split / cc_split_depth: entry(work_a, work_b, &K, &n_split, parent, cap) -> rc is the library's entry with
+        its leading arguments bound.  The parent table starts at 2 n + 2 rows; an entry that finds it too small reports K and leaves
+        the labels untouched, and is called once more with K + 1 rows."""
+        torch = self.torch
+        work_a = torch.empty(tuple(labels.shape), dtype=torch.int32, device=self.device)
+        work_b = torch.empty(tuple(labels.shape), dtype=torch.int32, device=self.device)
         k, n_split = C.c_uint64(), C.c_uint64()
         cap = 2 * n + 2
         self._enter()
@@ -955,9 +962,8 @@ class HipEngine:
             for attempt in (0, 1):
                 parent = torch.empty(cap, dtype=torch.int32, device=self.device)
                 k.value = 0
-                rc = self.lib.dlv_cc_split_dev(self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n, int(depth), int(min_core),
-                                               C.c_void_p(work_a.data_ptr()), C.c_void_p(work_b.data_ptr()), C.byref(k), C.byref(n_split),
-                                               C.c_void_p(parent.data_ptr()), cap)
+                rc = entry(C.c_void_p(work_a.data_ptr()), C.c_void_p(work_b.data_ptr()), C.byref(k), C.byref(n_split),
+                           C.c_void_p(parent.data_ptr()), cap)
                 if rc != 0 and attempt == 0 and int(k.value) + 1 > cap:  # (the table was too small: K is known now, the labels untouched)
                     cap = int(k.value) + 1
                     continue
@@ -967,6 +973,34 @@ class HipEngine:
             self._leave()
         K = int(k.value)
         return K, parent[:K + 1].cpu().numpy().view(np.uint32), int(n_split.value)
+
+    def cc_split_depth(self, labels, n: int, spacing, core_d2: int = 0, fraction: int = 0, min_core: int = 1):
+        """Fused cells split by their Euclidean depth cores, in place (dlv_cc_split_depth_dev): cc_split for stacks whose voxels
+        are not cubes.  labels: int32 (uint32 payload) (Z,Y,X) in HBM, contiguous, labels 0..n, no two different labels
+        26-adjacent (what ccl26, fill_holes and cc_size_filter give).  spacing: (wz, wy, wx), integers 1..64.  With D2 the exact
+        squared distance of a voxel to the outside of its label in spacing units (cc_depth) and m(l) the largest D2 of label l,
+        the cores are the voxels with D2 >= max(core_d2, ceil(fraction^2 * m(l) / 10000), 1): at least sqrt(core_d2) from the
+        outside, and at least `fraction` (0..99) per cent of the cell's inscribed radius; one of the two must be above 0.  From
+        there on as cc_split: cores 26-connected, those of fewer than `min_core` voxels dropped, a label with two or more cores
+        divided among them, all renumbered 1..K in raster order of their first voxel.  -> (K, parent: uint32 ndarray of K+1, the
+        number of labels that were split).  Needs two more volumes of the labels' size while it runs."""
+        Z, Y, X = self._label_volume("cc_split_depth", labels)
+        spacing = tuple(spacing) if isinstance(spacing, (tuple, list)) else (spacing,)
+        if len(spacing) != 3 or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= 64 for w in spacing):
+            raise ValueError(f"cc_split_depth: spacing = {spacing!r}: expected three integers 1..64 (wz, wy, wx)")
+        if isinstance(core_d2, bool) or not isinstance(core_d2, (int, np.integer)) or not 0 <= int(core_d2) <= 2**32 - 1:
+            raise ValueError(f"cc_split_depth: core_d2 = {core_d2!r}: expected an integer 0..2^32 - 1")
+        if isinstance(fraction, bool) or not isinstance(fraction, (int, np.integer)) or not 0 <= int(fraction) <= 99:
+            raise ValueError(f"cc_split_depth: fraction = {fraction!r}: expected an integer 0..99")
+        if int(core_d2) == 0 and int(fraction) == 0:
+            raise ValueError("cc_split_depth: core_d2 and fraction are both 0: no core is defined")
+        if isinstance(min_core, bool) or not isinstance(min_core, (int, np.integer)) or int(min_core) < 1:
+            raise ValueError(f"cc_split_depth: min_core = {min_core!r}: expected an integer >= 1")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"cc_split_depth: n = {n}")
+        return self._split_call(labels, n, lambda *tail: self.lib.dlv_cc_split_depth_dev(
+            self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n, *(int(w) for w in spacing), int(core_d2), int(fraction), int(min_core), *tail))
 
     def cc_runs_encode(self, labels) -> dict:
         """The run-length coding of a label volume in HBM (dlv_cc_runs_count_dev, dlv_cc_runs_emit_dev; the format and the numpy

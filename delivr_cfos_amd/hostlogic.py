@@ -1,6 +1,7 @@
 """Host-side integer logic of the path that the reference performs in Python (no device work)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -414,7 +415,8 @@ def split_fused_settings(settings):
     """count_blobs' split of fused cells: None when settings["mi355x"]["split_fused"] is absent, false or 0, else
     (depth, min_core): the erosion depth, an integer 1..16, and settings["mi355x"]["split_min_core"], the smallest core in voxels,
     an integer >= 1 (default 1).  ValueError for anything else (true, a float that is not integral, a string, a value outside the
-    range) and for split_min_core without split_fused."""
+    range) and for split_min_core without split_fused - unless split_radius or split_fraction is there, whose split it then belongs
+    to (split_depth_settings)."""
     mi = (settings or {}).get("mi355x") or {}
     value, min_core = mi.get("split_fused"), mi.get("split_min_core")
     off = value is None or value is False or (_is_integral(value) and int(value) == 0)
@@ -424,11 +426,49 @@ def split_fused_settings(settings):
     if min_core is not None and (not _is_integral(min_core) or int(min_core) < 1):
         raise ValueError(f"settings['mi355x']['split_min_core'] = {min_core!r}: expected the smallest core in voxels, an integer >= 1")
     if off:
-        if min_core is not None:
+        if min_core is not None and mi.get("split_radius") is None and mi.get("split_fraction") is None:
             raise ValueError(f"settings['mi355x']['split_min_core'] = {min_core!r} needs settings['mi355x']['split_fused']: it is the "
                              "smallest core the split counts")
         return None
     return int(value), 1 if min_core is None else int(min_core)
+
+
+SPLIT_MAX_CORE_D2 = 2**32 - 1  # dlv_cc_split_depth_dev's core_d2 is a uint32
+
+
+def split_depth_settings(settings):
+    """count_blobs' split of fused cells by Euclidean depth cores: None when settings["mi355x"] holds neither "split_radius" nor
+    "split_fraction", else (core_d2, fraction, min_core, spacing).  split_radius = r, an int or a float above 0 in the unit of
+    depth_spacing: a core voxel lies at least r from the outside of its cell, core_d2 = ceil(r * r) (0 without the key).
+    split_fraction = p, an integer 1..99: ... and at least p per cent of its cell's inscribed radius (0 without the key).  min_core:
+    split_min_core, as for split_fused.  spacing: depth_spacing = [wz, wy, wx], three integers 1..64 (default [1, 1, 1]).
+    ValueError for anything else (a bool, a radius that is not finite or whose square exceeds 2^32 - 1) and for either key together
+    with split_fused: the two splits are alternatives."""
+    mi = (settings or {}).get("mi355x") or {}
+    radius, fraction, min_core = mi.get("split_radius"), mi.get("split_fraction"), mi.get("split_min_core")
+    if radius is None and fraction is None:
+        return None
+    core_d2 = 0
+    if radius is not None:
+        if (isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not np.isfinite(radius)
+                or not radius > 0):
+            raise ValueError(f"settings['mi355x']['split_radius'] = {radius!r}: expected the distance of a core voxel from the outside "
+                             "of its cell, a number above 0 in the unit of depth_spacing")
+        core_d2 = int(math.ceil(float(radius) * float(radius))) if isinstance(radius, (float, np.floating)) else int(radius) ** 2
+        if core_d2 > SPLIT_MAX_CORE_D2:
+            raise ValueError(f"settings['mi355x']['split_radius'] = {radius!r}: its square, {core_d2}, exceeds {SPLIT_MAX_CORE_D2}")
+    if fraction is not None and (not _is_integral(fraction) or not 1 <= int(fraction) <= 99):
+        raise ValueError(f"settings['mi355x']['split_fraction'] = {fraction!r}: expected a percentage of the cell's inscribed radius, "
+                         "an integer 1..99")
+    if min_core is not None and (not _is_integral(min_core) or int(min_core) < 1):
+        raise ValueError(f"settings['mi355x']['split_min_core'] = {min_core!r}: expected the smallest core in voxels, an integer >= 1")
+    if split_fused_settings(settings) is not None:
+        key = "split_radius" if radius is not None else "split_fraction"
+        raise ValueError(f"settings['mi355x']['split_fused'] = {mi.get('split_fused')!r} and settings['mi355x']['{key}'] = {mi.get(key)!r} "
+                         "are alternatives: erosion cores counted in voxels, or depth cores in the unit of depth_spacing; give one")
+    spacing = _depth_spacing(mi)
+    return (core_d2, 0 if fraction is None else int(fraction), 1 if min_core is None else int(min_core),
+            (1, 1, 1) if spacing is None else spacing)
 
 
 def finish_split(parent, n_before: int) -> dict:
@@ -595,26 +635,36 @@ DEPTH_MAX_SPACING = 64  # dlv_cc_depth_dev's largest spacing
 _DEPTH_RAW_DTYPES = (np.uint32, np.uint64, np.uint64)
 
 
+def _depth_spacing(mi):
+    """settings["mi355x"]["depth_spacing"] as a tuple (wz, wy, wx), None without the key; ValueError for anything but three integers
+    1..64"""
+    spacing = mi.get("depth_spacing")
+    if spacing is None:
+        return None
+    if (not isinstance(spacing, (list, tuple)) or len(spacing) != 3
+            or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= DEPTH_MAX_SPACING for w in spacing)):
+        raise ValueError(f"settings['mi355x']['depth_spacing'] = {spacing!r}: expected the voxel spacing [wz, wy, wx], three "
+                         f"integers 1..{DEPTH_MAX_SPACING}")
+    return tuple(int(w) for w in spacing)
+
+
 def depth_stats_settings(settings):
     """count_blobs' per-cell depth: None when settings["mi355x"]["depth_stats"] is absent or false, else the voxel spacing
     (wz, wy, wx) of the distance map: settings["mi355x"]["depth_spacing"], three integers 1..64 (default [1, 1, 1]).  ValueError for
     a depth_stats that is not a bool, for a spacing that is anything else (a bool, a float, two values, a value outside the range)
-    and for depth_spacing without depth_stats."""
+    and for depth_spacing without depth_stats - unless split_radius or split_fraction is there, which measure with it too."""
     mi = (settings or {}).get("mi355x") or {}
-    value, spacing = mi.get("depth_stats"), mi.get("depth_spacing")
+    value = mi.get("depth_stats")
     if value is not None and value is not True and value is not False:
         raise ValueError(f"settings['mi355x']['depth_stats'] = {value!r}: expected true or false")
-    if spacing is not None:
-        if (not isinstance(spacing, (list, tuple)) or len(spacing) != 3
-                or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= DEPTH_MAX_SPACING for w in spacing)):
-            raise ValueError(f"settings['mi355x']['depth_spacing'] = {spacing!r}: expected the voxel spacing [wz, wy, wx], three "
-                             f"integers 1..{DEPTH_MAX_SPACING}")
+    spacing = _depth_spacing(mi)
     if not value:
-        if spacing is not None:
-            raise ValueError(f"settings['mi355x']['depth_spacing'] = {spacing!r} needs settings['mi355x']['depth_stats']: it is the "
-                             "voxel spacing of the depth map")
+        # (split_radius / split_fraction measure with the same spacing: split_depth_settings)
+        if spacing is not None and mi.get("split_radius") is None and mi.get("split_fraction") is None:
+            raise ValueError(f"settings['mi355x']['depth_spacing'] = {mi.get('depth_spacing')!r} needs settings['mi355x']['depth_stats']: "
+                             "it is the voxel spacing of the depth map")
         return None
-    return (1, 1, 1) if spacing is None else tuple(int(w) for w in spacing)
+    return (1, 1, 1) if spacing is None else spacing
 
 
 def finish_depth(raw: dict, voxel_counts, shape, spacing) -> dict:
@@ -721,6 +771,7 @@ class CountOptions:
     label_file: str = "dense"  # label_file_format
     confidence: bool = False  # confidence_stats_enabled
     depth: Optional[Tuple[int, int, int]] = None  # depth_stats_settings
+    split_depth: Optional[Tuple[int, int, int, Tuple[int, int, int]]] = None  # split_depth_settings: (core_d2, fraction, min_core, spacing)
     fill_holes: bool = False  # fill_holes_enabled (the last field: tests/test_fill_holes_cpu.py pins it)
 
     @property
@@ -746,13 +797,14 @@ def count_options(settings, min_size, max_size) -> CountOptions:
     shell_radius = background_shell_radius(settings)
     quartiles = intensity_quartiles_enabled(settings)
     split = split_fused_settings(settings)
+    split_depth = split_depth_settings(settings)
     shape = shape_stats_enabled(settings)
     confidence = confidence_stats_enabled(settings)
     fill = fill_holes_enabled(settings)
     depth = depth_stats_settings(settings)
     return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
                         shape=shape, split=split, label_file=label_file_format(settings), confidence=confidence,
-                        fill_holes=fill, depth=depth)
+                        fill_holes=fill, depth=depth, split_depth=split_depth)
 
 
 INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
@@ -789,7 +841,7 @@ def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
 
 
-_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "depth_stats", "split_fused", "size_filter", "label_file")
+_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "depth_stats", "split_fused", "split_radius", "size_filter", "label_file")
 _HBM_CACHED = ("label_file", "shape_stats", "depth_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
 
 
@@ -817,6 +869,8 @@ def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxe
         "depth_stats": ("depth" in measured, "", 8, f"8 more bytes per voxel in HBM beside {resident}", "measure"),
         "split_fused": (opts.split is not None, f" = {opts.split and opts.split[0]}", 8,
                         f"8 more bytes per voxel in HBM beside {resident}", "split"),
+        "split_radius": (opts.split_depth is not None, " / ['split_fraction']", 8,
+                         f"8 more bytes per voxel in HBM beside {resident}", "split"),
         "size_filter": (opts.filter_active, "", 0, f"{resident} in HBM", "filter"),
         "label_file": (opts.runs_file and (runs_decoded or not cached), ' = "runs"', 0, f"{resident} in HBM", "write run-length labels"),
     }

@@ -397,6 +397,28 @@ int dlv_cc_depth_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int
 int dlv_cc_split_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int depth, int64_t min_core,
                      uint32_t* work_a_dev, uint32_t* work_b_dev, uint64_t* n_out, uint64_t* n_split_out,
                      uint32_t* parent_dev, uint64_t parent_cap);
+/* Fused cells split by their Euclidean depth cores (no counterpart in the reference; csrc/cc_split.hip): dlv_cc_split_dev with the
+ * cores taken from the exact label-wise distance map instead of voxel-counted erosions, for stacks whose voxels are not cubes - a
+ * Euclidean erosion in physical units. labels_dev: uint32 (Z,Y,X) contiguous, labels 0..n, rewritten in place. PRECONDITION: no two
+ * different labels are 26-adjacent - what dlv_ccl26_dev, dlv_fill_holes_dev and dlv_cc_size_filter_dev produce; only then does a core
+ * lie in one label. Where it is broken the result is unspecified, but every access stays in bounds.
+ * (1) The distance map: D2(v) is what dlv_cc_depth_dev defines on labels_dev with the spacings wz, wy, wx (integers 1..64);
+ * m(l) = the largest D2 of label l. (2) Cores: T(l) = max(core_d2, ceil(core_pct^2 * m(l) / 10000), 1) in 64-bit integers;
+ * C(v) = 1 where 1 <= labels(v) <= n and D2(v) >= T(labels(v)), else 0: every voxel at least sqrt(core_d2) spacing units, and at
+ * least core_pct per cent of its cell's inscribed radius, from the outside of its cell. With core_pct > 0 every label present holds
+ * at least one core, the one around its peak; with core_d2 > m(l) a label has no core and stays whole. (3), (4): the cores are
+ * labelled, filtered by min_core, grown back through their own label and the pieces numbered exactly as steps (2) - (4) of
+ * dlv_cc_split_dev say, by the same code: *n_out = K, *n_split_out, parent_dev and parent_cap are that entry's, labels_dev unchanged
+ * and *n_out = K when the table is too small. Integer work only: exact and independent of scheduling.
+ * work_a_dev, work_b_dev: two scratch volumes of Z*Y*X uint32 (D2, then the byte mask of the cores beside it: no more than
+ * dlv_cc_split_dev needs). DLV_EINVAL before any launch, labels_dev unchanged, for a NULL pointer, Z/Y/X < 1, a spacing outside
+ * 1..64, core_pct outside 0..99, core_d2 == 0 together with core_pct == 0, min_core < 1, a pointer that is not 4-byte aligned,
+ * volumes that overlap, n >= 2^32 - 1 or a volume beyond the launch grid; DLV_EUNSUP before any launch for the reach rule of
+ * dlv_cc_depth_dev (w_a * ceil((dim_a + 1) / 2) >= 65536) and above 2^32 voxels. DLV_EINVAL with labels_dev unchanged for a label
+ * above n in the volume (found after the seed pass, as in dlv_cc_split_dev) and for M + n beyond the uint32 keys. Synchronous. */
+int dlv_cc_split_depth_dev(dlv_ctx* ctx, uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                           uint32_t core_d2, int core_pct, int64_t min_core, uint32_t* work_a_dev, uint32_t* work_b_dev,
+                           uint64_t* n_out, uint64_t* n_split_out, uint32_t* parent_dev, uint64_t parent_cap);
 /* The run-length coding of a label volume and its decoder (no counterpart in the reference, which writes the dense volume; the
  * format: delivr_cfos_amd/label_runs.py). labels_dev: uint32 (Z,Y,X) contiguous, 4-byte aligned, labels below 2^32 - 1. A run is a
  * maximal stretch of one non-zero label inside a row (z, y): it never crosses a row's end, and two touching runs of different labels

@@ -251,6 +251,10 @@ SIGNATURES = {
     "dlv_cc_overlap_count_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dlv_cc_overlap_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P, _P,
                                      C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dlv_cc_neighbours_count_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                              C.POINTER(C.c_uint64)]),
+    "dlv_cc_neighbours_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
+                                        _P, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dlv_paint_owner_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_uint64, _P]),
     "dlv_paint_apply_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_int, _P]),
     "dlv_paint_labels_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, _P]),

@@ -17,8 +17,9 @@ import numpy as np
 
 from . import hostio, label_runs
 from .hostlogic import (FILL_VALUE, QUARTILE_LEVELS, RAW_GROUPS, SHELL_KEYS, SHELL_QUARTILE_KEYS, CountOptions, cell_confidence_csv_text,
-                        cell_depth_csv_text, cell_holes_csv_text, cell_intensity_csv_text, cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
-                        count_options, csv_name, finish_confidence, finish_depth, finish_intensity, finish_quartiles, finish_shape, finish_shell,
+                        cell_depth_csv_text, cell_holes_csv_text, cell_intensity_csv_text, cell_neighbours_csv_text, cell_pairs_csv_text,
+                        cell_quartiles_csv_text, cell_shape_csv_text, cells_csv_bytes, check_hbm_budget,
+                        count_options, csv_name, finish_confidence, finish_depth, finish_intensity, finish_neighbours, finish_quartiles, finish_shape, finish_shell,
                         finish_shell_quartiles, finish_split, measuring_plan, merge_confidence, merge_intensity, merge_shape,
                         merge_shell)
 
@@ -113,6 +114,19 @@ def _note_fill(voxels_filled: int, holes: int, n_after: int):
     # (the components before the fill are not named: the cells a cavity swallowed are only known from a second labelling)
     count_blobs.last_fill = {"holes": int(holes), "voxels_filled": int(voxels_filled), "n_after": int(n_after)}
     print(f"fill of holes: {holes} holes filled, {voxels_filled} voxels added, {n_after} components after the fill")
+
+
+def _note_neighbours(neighbours, stats, n: int):
+    radius_sq, spacing = neighbours
+    pairs = int(len(stats["neighbour_gap_sq"]))
+    sizes = np.asarray(stats["cluster_size"])[1:n + 1]
+    ids = np.asarray(stats["cluster_id"])[1:n + 1]
+    clusters = int(len(np.unique(ids[sizes >= 2])))
+    alone = int(np.count_nonzero(np.asarray(stats["neighbour_count"])[1:n + 1] == 0))
+    count_blobs.last_neighbours = {"n": int(n), "radius_sq": int(radius_sq), "spacing": tuple(int(w) for w in spacing), "pairs": pairs,
+                                   "clusters": clusters, "cells_without_neighbour": alone}
+    print(f"cell neighbourhoods (radius_sq {radius_sq}, spacing {list(spacing)}): {pairs} pairs, {clusters} clusters of two or more "
+          f"cells, {alone} of {n} cells without a neighbour")
 
 
 def _open_raw_volume(settings, brain, shape):
@@ -248,7 +262,7 @@ def _write_table(path_out, folder, brain, text):
 
 def _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file=None):
     """the tables of the opt-in statistics `opts` asks for, and what count_blobs.last_intensity / last_quartiles / last_shape /
-    last_confidence / last_depth say"""
+    last_confidence / last_depth / last_neighbours say"""
     def for_table(shell_keys):  # (shell entries of a cached pickle do not reach the table of a run without the key)
         return stats if opts.shell_radius else {k: v for k, v in stats.items() if k not in shell_keys}
 
@@ -269,6 +283,10 @@ def _write_tables(path_out, brain, stats, N, opts, raw_file, prob_file=None):
     if opts.depth is not None:
         _write_table(path_out, "cell_depth", brain, cell_depth_csv_text(stats, N))
         count_blobs.last_depth = {"n": int(N), "spacing": tuple(opts.depth)}
+    if opts.neighbours is not None:
+        _write_table(path_out, "cell_neighbours", brain, cell_neighbours_csv_text(stats, N))
+        _write_table(path_out, "cell_pairs", brain, cell_pairs_csv_text(stats))
+        _note_neighbours(opts.neighbours, stats, N)
     if opts.fill_holes and "hole_voxels" in stats:  # (a cached labelling is not filled: its pickle may lack the key)
         _write_table(path_out, "cell_holes", brain, cell_holes_csv_text(stats, N))
 
@@ -550,7 +568,23 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     gains depth_s.  Cached labels - dense or decoded runs - are measured too, and a cached pickle without the keys, or with another
     depth_spacing, is completed.  Needs 8 more bytes of HBM per voxel while it runs; a mask that needs the slab-streamed path is
     refused (MemoryError).  Under torch.distributed the key is refused with ValueError on every rank: a cell that crosses a slab cut
-    has its nearest outside voxel on another rank.  Off or absent: nothing of this happens, and no new kernel is launched."""
+    has its nearest outside voxel on another rank.  Off or absent: nothing of this happens, and no new kernel is launched.
+
+    ``settings["mi355x"]["neighbour_stats"]`` = r (a number above 0 in the unit of ``depth_spacing``, default [1, 1, 1]; on its own: no
+    raw volume is opened): how the cells lie relative to each other.  Two cells are neighbours when a voxel of one lies within r of
+    a voxel of the other; their gap is the exact smallest such distance, squared, in integers (R2 = floor(r * r); along every axis
+    r may reach at most 8 voxels - a larger radius is a ValueError that names the axis).  The table is taken on the final labels on
+    the device (HipEngine.cc_neighbours), after fill, split and filter, where depth_stats is measured.  The pickle gains
+    neighbour_pairs (uint32 (P, 2), a < b, sorted), neighbour_gap_sq (uint32 (P)), neighbour_radius_sq, neighbour_spacing and the
+    per-cell rows of hostlogic.neighbour_summary: neighbour_count, nearest_gap_sq and nearest_cell (0: no neighbour within r),
+    cluster_id and cluster_size (the connected components of the graph; a cell without a neighbour is its own cluster).  The tables
+    go to <output_location>/cell_neighbours/<brain>.csv (one row per cell) and <output_location>/cell_pairs/<brain>.csv (one row per
+    pair), ``count_blobs.last_neighbours`` holds {"n", "radius_sq", "spacing", "pairs", "clusters", "cells_without_neighbour"} and
+    ``count_blobs.last_timings`` gains neighbours_s.  Cached labels - dense or decoded runs - are measured too, and a cached pickle
+    without the keys, or with another neighbour_radius_sq or neighbour_spacing, is completed.  Needs only the labels in HBM beside
+    the pair table, which is sized from a counting pass and checked against the HBM budget; a mask that needs the slab-streamed
+    path is refused (MemoryError).  Under torch.distributed the key is refused with ValueError on every rank: two neighbouring cells
+    can lie on either side of a slab cut.  Off, 0 or absent: nothing of this happens, and no new kernel is launched."""
     from .engine import shared_engine
 
     count_blobs.last_filter = None  # set by a run that filtered
@@ -561,6 +595,7 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
     count_blobs.last_confidence = None  # set by a run with settings["mi355x"]["confidence_stats"]
     count_blobs.last_fill = None  # set by a run that filled holes (settings["mi355x"]["fill_holes"])
     count_blobs.last_depth = None  # set by a run with settings["mi355x"]["depth_stats"]
+    count_blobs.last_neighbours = None  # set by a run with settings["mi355x"]["neighbour_stats"]
     opts = count_options(settings, min_size, max_size)  # (a bad key raises here, before any file is touched)
     split, shell_radius = opts.split, opts.shell_radius
     if opts.bounds is None and any(v is not None and int(v) >= 0 for v in (min_size, max_size)):
@@ -595,6 +630,11 @@ def count_blobs(settings, path_in, brain_i, brain, stack_shape, min_size=-1, max
         raise ValueError(f"count_blobs: settings['mi355x']['depth_stats'] is not available under torch.distributed "
                          f"({dist.get_world_size()} ranks): a cell that crosses a slab cut has its nearest outside voxel on another "
                          "rank, so a Z-slab cannot be measured on its own; run step 3 on one device or switch depth_stats off")
+    if sharded and opts.neighbours is not None:
+        # (as for split_fused: all raise, before any collective, or none does)
+        raise ValueError(f"count_blobs: settings['mi355x']['neighbour_stats'] is not available under torch.distributed "
+                         f"({dist.get_world_size()} ranks): two neighbouring cells can lie on either side of a slab cut, so a Z-slab "
+                         "cannot be measured on its own; run step 3 on one device or switch neighbour_stats off")
     if sharded and opts.runs_file:
         # (as for split_fused: all raise, before any collective, or none does)
         raise ValueError(f"count_blobs: settings['mi355x']['label_file'] = \"runs\" is not available under torch.distributed "
@@ -717,7 +757,8 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
     scratch volumes of the split are gone before the raw volume is uploaded, so the two peaks do not add.  The labels - fresh or
     cached - are measured after cc_stats: what hostlogic.measuring_plan finds missing, from one upload of raw_vol (_measure_raw), then
     the confidence from one upload of prob_vol (_measure_confidence: the raw tensor is gone by then), then the shape accumulators,
-    then the depth (HipEngine.cc_depth); the pickle is written once, after the last of these."""
+    then the depth (HipEngine.cc_depth), then the neighbour table (HipEngine.cc_neighbours); the pickle is written once, after the
+    last of these."""
     import time
 
     bounds, split = opts.bounds, opts.split
@@ -927,7 +968,7 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             if got.shell_quartiles is not None:
                 stats.update(finish_shell_quartiles(*got.shell_quartiles, stats["shell_voxels"], stats["intensity_median"]))
             # (a cached pickle without the keys is rewritten: the keys added, its entries untouched)
-            if not plan & {"confidence", "shape", "depth"}:
+            if not plan & {"confidence", "shape", "depth", "neighbours"}:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))
             mark("intensity")
             if opts.quartiles:  # (HipEngine.cc_quantiles is synchronous: its share of the time since the last mark)
@@ -937,14 +978,14 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
             stats.update(finish_confidence(_measure_confidence(eng, labels_dev, prob_vol, N), stats["voxel_counts"], bin_img.shape))
-            if not plan & {"shape", "depth"}:
+            if not plan & {"shape", "depth", "neighbours"}:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
             mark("confidence")
         if "shape" in plan:
             if labels_dev is None:
                 labels_dev = cached_labels_to_device()
             stats.update(finish_shape(eng.cc_shape(labels_dev, N), stats["voxel_counts"]))
-            if "depth" not in plan:
+            if not plan & {"depth", "neighbours"}:
                 write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
             mark("shape")
         if "depth" in plan:
@@ -952,8 +993,17 @@ def _count_blobs_single(settings, brain, bin_img, eng, path_out, start, opts=Cou
                 labels_dev = cached_labels_to_device()
             # (the two scratch volumes of the distance map are gone when cc_depth returns)
             stats.update(finish_depth(eng.cc_depth(labels_dev, N, opts.depth), stats["voxel_counts"], bin_img.shape, opts.depth))
-            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
+            if "neighbours" not in plan:
+                write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
             mark("depth")
+        if "neighbours" in plan:
+            if labels_dev is None:
+                labels_dev = cached_labels_to_device()
+            radius_sq, spacing = opts.neighbours
+            # (the pair table and the outputs are sized from the count and checked against the HBM budget in there)
+            stats.update(finish_neighbours(eng.cc_neighbours(labels_dev, N, spacing, radius_sq, settings=settings), N, radius_sq, spacing))
+            write_stats(cached_stats or os.path.join(path_out, f"{brain}-stats.pickle"))  # (as above: completed, not replaced)
+            mark("neighbours")
     except BaseException:
         try:
             wait()  # (do not leave the writer thread behind an error of this one)

@@ -8,7 +8,7 @@
 // differs from the key of the voxel before it (0 outside the row and for a voxel that takes no part), which a lane learns from the
 // lane below it (lane 0: from memory).  The number of segments S bounds the number of distinct pairs P, and so does n_a * n_b: the
 // caller sizes the table and the outputs from min(S, n_a * n_b).
-// Insert.  An open-addressed table in HBM: cap slots (a power of two >= 2 * min(S, n_a * n_b)) of {uint64 key, uint64 voxels},
+// Insert.  An open-addressed table in HBM (cc_pair_table.h, shared with cc_neighbours.hip): cap slots (a power of two >= 2 * min(S, n_a * n_b)) of {uint64 key, uint64 voxels},
 // zeroed first, key 0 = empty.  A key is hashed with the 64-bit finaliser of splitmix64 and probed linearly: a relaxed load of the
 // slot's key, a 64-bit compare-and-swap where it reads empty, and a 64-bit atomic add on the voxels of the slot that holds the key.
 // Contributions are combined before they reach memory, in three steps:
@@ -39,6 +39,7 @@
 #include "common.h"
 #include "cc_check.h"
 #include "cc_fold.h"
+#include "cc_pair_table.h"
 
 #include <algorithm>
 
@@ -46,17 +47,7 @@ namespace {
 
 constexpr int OT = 64;                    // threads per workgroup: one wave, one row at a time
 constexpr u64 OVERLAP_MAX_WG = 256 * 32;  // workgroups per launch; rows beyond that are walked grid-stride
-constexpr int CT = 256;                   // threads per workgroup of the compaction
-constexpr int CPL = 8;                    // slots per lane and trip of the compaction
-constexpr int CSLOTS = 64 * CPL;          // ... and per wave: one cursor atomic per 512 slots
-constexpr u64 COMPACT_MAX_WG = 256 * 8;
 constexpr int MAX_X = 1 << 30;            // (the sweep arithmetic is 32-bit)
-
-typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
-
-// device words of one call: [0] the segments / the compaction's cursor, [1] the overflow word
-enum { W_COUNT = 0, W_OVERFLOW = 1, W_WORDS = 2 };
-constexpr u64 OVERFLOW_TABLE = 1, OVERFLOW_OUT = 2;
 
 // The keys of this lane's two quads of sweep sw of row r (0: the voxel takes no part or lies past the row's end).  Returns false -
 // for the whole wave - where the sweep holds no key.
@@ -113,26 +104,9 @@ __global__ void __launch_bounds__(OT) cc_overlap_count_kernel(const u32* __restr
 }
 
 // ---- insert ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 mix64(u64 x) {  // splitmix64's finaliser
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
-// voxels of `key` into its slot: at most cap probes, the overflow word where no slot is left
+// voxels of `key` into its slot (cc_pair_table.h: at most cap probes, the overflow word where no slot is left)
 __device__ __forceinline__ void table_add(u64* __restrict__ table, u64 cap, u64 key, u64 voxels, u64* __restrict__ words) {
-    const u64 mask = cap - 1;
-    u64 slot = mix64(key) & mask;
-    for (u64 i = 0; i < cap; ++i, slot = (slot + 1) & mask) {
-        u64* at = table + 2 * slot;
-        u64 held = __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (a key, once set, never changes)
-        if (held == 0) held = atomicCAS(at, 0ull, key);                                // (returns what was there: 0 = the slot is ours now)
-        if (held == 0 || held == key) {
-            atomicAdd(at + 1, voxels);
-            return;
-        }
-    }
-    atomicOr(words + W_OVERFLOW, OVERFLOW_TABLE);
+    if (u64* at = pair_slot(table, cap, key, words)) atomicAdd(at, voxels);
 }
 
 // THE LEADER LOOP ON A 64-BIT KEY, the twin of cc_fold.h's wave_fold_by_label: the lanes of a wave that hold the same key are
@@ -225,45 +199,6 @@ __global__ void __launch_bounds__(OT) cc_overlap_insert_kernel(const u32* __rest
     flush();
 }
 
-// ---- compact: the occupied slots, in no particular order ---------------------------------------------------------------------
-__global__ void __launch_bounds__(CT) cc_overlap_compact_kernel(const u64* __restrict__ table, u64 cap, u64* __restrict__ keys_out,
-                                                                u64* __restrict__ voxels_out, u64 out_cap, u64* __restrict__ words) {
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const u64 stride = (u64)gridDim.x * (CT / 64) * CSLOTS;
-    // a wave takes CSLOTS slots per trip, CPL rounds of 64 neighbours (wave-uniform trip count)
-    for (u64 first = ((u64)blockIdx.x * (CT / 64) + (threadIdx.x >> 6)) * CSLOTS; first < cap; first += stride) {
-        u64x2_t s[CPL];
-        unsigned long long m[CPL];
-        u32 total = 0;
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-            const u64 slot = first + (u64)j * 64 + lane;
-            s[j] = u64x2_t{0ull, 0ull};
-            if (slot < cap) s[j] = *reinterpret_cast<const u64x2_t*>(table + 2 * slot);
-            m[j] = __ballot(s[j].x != 0);
-            total += (u32)__popcll(m[j]);
-        }
-        if (!total) continue;
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(words + W_COUNT, (u64)total);
-        base = shfl64(base, 0);
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-            if (s[j].x != 0) {
-                const u64 at = base + (u64)__popcll(m[j] & below);
-                if (at < out_cap) {
-                    keys_out[at] = s[j].x;
-                    voxels_out[at] = s[j].y;
-                } else {
-                    atomicOr(words + W_OVERFLOW, OVERFLOW_OUT);
-                }
-            }
-            base += (u64)__popcll(m[j]);
-        }
-    }
-}
-
 // what both entries check of the volumes, before anything is launched
 int overlap_args(dlv_ctx* ctx, const char* what, const void* a_dev, const void* b_dev, int Z, int Y, int X, uint64_t n_a, uint64_t n_b) {
     DLV_TRY(check_volume(ctx, what, Z, Y, X));
@@ -337,13 +272,11 @@ int dlv_cc_overlap_dev(dlv_ctx* ctx, const uint32_t* a_dev, const uint32_t* b_de
     DLV_LAUNCH_CHECK(ctx, "cc_overlap_insert_kernel");
     {
         DlvProf pr(ctx, "cc_overlap_compact", 0.0, (double)cap * 16);
-        const u64 per_wg = (u64)(CT / 64) * CSLOTS;
-        const unsigned grid = (unsigned)std::min<u64>((cap + per_wg - 1) / per_wg, COMPACT_MAX_WG);
-        hipLaunchKernelGGL(cc_overlap_compact_kernel, dim3(grid), dim3(CT), 0, ctx->stream, (const u64*)table_dev, (u64)cap, (u64*)keys_out_dev,
-                           (u64*)voxels_out_dev, (u64)out_cap, words);
+        hipLaunchKernelGGL(pair_table_compact_kernel<u64>, dim3(pair_table_compact_grid(cap)), dim3(PT_CT), 0, ctx->stream, (const u64*)table_dev,
+                           (u64)cap, (u64*)keys_out_dev, (u64*)voxels_out_dev, (u64)out_cap, words);
         pr.end();
     }
-    DLV_LAUNCH_CHECK(ctx, "cc_overlap_compact_kernel");
+    DLV_LAUNCH_CHECK(ctx, "pair_table_compact_kernel");
     u64 host[W_WORDS] = {0, 0};
     DLV_HIP(ctx, hipMemcpyAsync(host, words, W_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream));
     DLV_HIP(ctx, hipStreamSynchronize(ctx->stream));

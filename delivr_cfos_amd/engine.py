@@ -1107,6 +1107,62 @@ class HipEngine:
         return {"a": (key >> np.uint64(32)).astype(np.uint32), "b": (key & np.uint64(0xFFFFFFFF)).astype(np.uint32),
                 "voxels": np.ascontiguousarray(vox[order]), "segments": S}
 
+    def cc_neighbours(self, labels, n: int, spacing=(1, 1, 1), radius_sq: int = 1, settings=None) -> dict:
+        """The neighbour table of a label volume in HBM (dlv_cc_neighbours_count_dev, dlv_cc_neighbours_dev; the numpy statement:
+        tests/helpers/neighbour_reference.py).  labels: int32 (uint32 payload) (Z,Y,X) in HBM, contiguous, not modified.  A voxel
+        takes part when 1 <= label <= n.  spacing: (wz, wy, wx), integers 1..64; radius_sq: an integer >= 1, in spacing units.
+        -> {"a", "b": uint32 (P), "gap_sq": uint32 (P), "segments": S}: the P pairs of labels a < b whose cells come within
+        sqrt(radius_sq) of each other, sorted by (a, b) and unique, with the exact smallest squared distance between a voxel of one
+        and a voxel of the other; S = the segments of the scan, which sized the table.  ValueError for a reach
+        floor(sqrt(radius_sq) / w) above hostlogic.NEIGHBOUR_MAX_REACH voxels on an axis.  The table (32 bytes per
+        min(S, n (n - 1) / 2), rounded up to a power of two) and the outputs (12 bytes each) must fit the HBM budget
+        (streaming.hbm_budget_bytes of `settings`): MemoryError names the sizes."""
+        from .hostlogic import neighbour_reach
+
+        torch = self.torch
+        Z, Y, X = self._label_volume("cc_neighbours", labels)
+        spacing = tuple(spacing) if isinstance(spacing, (tuple, list)) else (spacing,)
+        if len(spacing) != 3 or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= 64 for w in spacing):
+            raise ValueError(f"cc_neighbours: spacing = {spacing!r}: expected three integers 1..64 (wz, wy, wx)")
+        if isinstance(radius_sq, bool) or not isinstance(radius_sq, (int, np.integer)) or int(radius_sq) < 1:
+            raise ValueError(f"cc_neighbours: radius_sq = {radius_sq!r}: expected an integer >= 1")
+        n, r2 = int(n), int(radius_sq)
+        if n < 0:
+            raise ValueError(f"cc_neighbours: n = {n}")
+        neighbour_reach(r2, spacing, "cc_neighbours: radius_sq")  # (ValueError that names the axis)
+        empty = {"a": np.zeros(0, dtype=np.uint32), "b": np.zeros(0, dtype=np.uint32), "gap_sq": np.zeros(0, dtype=np.uint32), "segments": 0}
+        head = (self.ctx, C.c_void_p(labels.data_ptr()), Z, Y, X, n, *(int(w) for w in spacing), r2)
+        s, p = C.c_uint64(), C.c_uint64()
+        self._enter()
+        try:
+            self._check(self.lib.dlv_cc_neighbours_count_dev(*head, C.byref(s)))
+            S = int(s.value)
+            bound = min(S, n * (n - 1) // 2)
+            if bound == 0:
+                return empty
+            cap = 1 << (2 * bound - 1).bit_length()  # the power of two >= 2 * bound
+            from .streaming import hbm_budget_bytes
+
+            need, budget = cap * 16 + bound * 12, hbm_budget_bytes(self, settings)
+            if need > budget:
+                raise MemoryError(f"delivr_cfos_amd (DLV_ENOMEM): cc_neighbours needs a pair table of {cap} slots ({cap * 16 / 2**30:.2f} GiB) "
+                                  f"and outputs of {bound} pairs ({bound * 12 / 2**30:.2f} GiB) for {S} segments of {n} labels, the HBM "
+                                  f"budget is {budget / 2**30:.2f} GiB; take a smaller radius, or raise settings['mi355x']['hbm_budget_gb']")
+            table = torch.empty(2 * cap, dtype=torch.int64, device=self.device)  # uint64 payloads
+            keys = torch.empty(bound, dtype=torch.int64, device=self.device)
+            gaps = torch.empty(bound, dtype=torch.int32, device=self.device)  # uint32 payloads
+            self._check(self.lib.dlv_cc_neighbours_dev(*head, S, C.c_void_p(table.data_ptr()), cap, C.c_void_p(keys.data_ptr()),
+                                                       C.c_void_p(gaps.data_ptr()), bound, C.byref(p)))
+        finally:
+            self._leave()
+        P = int(p.value)
+        key = keys[:P].cpu().numpy().view(np.uint64)
+        gap = gaps[:P].cpu().numpy().view(np.uint32)
+        order = np.argsort(key, kind="stable")  # (the device order is unspecified)
+        key = key[order]
+        return {"a": (key >> np.uint64(32)).astype(np.uint32), "b": (key & np.uint64(0xFFFFFFFF)).astype(np.uint32),
+                "gap_sq": np.ascontiguousarray(gap[order]), "segments": S}
+
     # ---- blob painting -----------------------------------------------------------------------------
     def edt_u16(self, stack, sampling_zyx):
         """blob_depthmap.py:160-170: exact Euclidean distance (units of `sampling_zyx`) of every non-zero voxel of the

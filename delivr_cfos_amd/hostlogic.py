@@ -652,15 +652,16 @@ def depth_stats_settings(settings):
     """count_blobs' per-cell depth: None when settings["mi355x"]["depth_stats"] is absent or false, else the voxel spacing
     (wz, wy, wx) of the distance map: settings["mi355x"]["depth_spacing"], three integers 1..64 (default [1, 1, 1]).  ValueError for
     a depth_stats that is not a bool, for a spacing that is anything else (a bool, a float, two values, a value outside the range)
-    and for depth_spacing without depth_stats - unless split_radius or split_fraction is there, which measure with it too."""
+    and for depth_spacing without depth_stats - unless split_radius, split_fraction or neighbour_stats is there, which measure with it
+    too."""
     mi = (settings or {}).get("mi355x") or {}
     value = mi.get("depth_stats")
     if value is not None and value is not True and value is not False:
         raise ValueError(f"settings['mi355x']['depth_stats'] = {value!r}: expected true or false")
     spacing = _depth_spacing(mi)
     if not value:
-        # (split_radius / split_fraction measure with the same spacing: split_depth_settings)
-        if spacing is not None and mi.get("split_radius") is None and mi.get("split_fraction") is None:
+        # (split_radius / split_fraction / neighbour_stats measure with the same spacing: split_depth_settings, neighbour_stats_settings)
+        if spacing is not None and mi.get("split_radius") is None and mi.get("split_fraction") is None and not _neighbour_stats_given(mi):
             raise ValueError(f"settings['mi355x']['depth_spacing'] = {mi.get('depth_spacing')!r} needs settings['mi355x']['depth_stats']: "
                              "it is the voxel spacing of the depth map")
         return None
@@ -713,6 +714,136 @@ def cell_depth_csv_text(stats: dict, n: int) -> str:
         raise ValueError("statistics shorter than the label count")
     lines = ["Blob,Size,Radius,MeanSqDepth,PeakZ,PeakY,PeakX"]
     lines.extend(f"{i},{c},{r!r},{m!r},{z},{y},{x}" for i, (c, r, m, (z, y, x)) in enumerate(zip(counts, *floats, peak), 1))
+    return "\n".join(lines) + "\n"
+
+NEIGHBOUR_KEYS = ("neighbour_pairs", "neighbour_gap_sq", "neighbour_radius_sq", "neighbour_spacing", "neighbour_count", "nearest_gap_sq",
+                  "nearest_cell", "cluster_id", "cluster_size")  # what settings["mi355x"]["neighbour_stats"] adds to the statistics
+NEIGHBOUR_MAX_REACH = 8  # dlv_cc_neighbours_dev's largest reach in voxels along an axis (NB_MAX_REACH of csrc/cc_neighbours.hip)
+
+
+def _neighbour_stats_given(mi) -> bool:
+    """settings["mi355x"]["neighbour_stats"] is there and not switched off (absent, false or 0)"""
+    value = mi.get("neighbour_stats")
+    return value is not None and value is not False and not (_is_number(value) and value == 0)
+
+
+def _is_number(value) -> bool:
+    return not isinstance(value, (bool, np.bool_)) and isinstance(value, (int, float, np.integer, np.floating))
+
+
+def neighbour_reach(radius_sq: int, spacing, what: str) -> Tuple[int, int, int]:
+    """The reach of a squared radius along z, y, x in voxels, floor(sqrt(radius_sq) / w); ValueError, starting with `what` and naming
+    the axis, its reach and the limit, where one exceeds NEIGHBOUR_MAX_REACH."""
+    root = math.isqrt(int(radius_sq))
+    reach = tuple(root // int(w) for w in spacing)
+    for axis, w, rho in zip("zyx", spacing, reach):
+        if rho > NEIGHBOUR_MAX_REACH:
+            raise ValueError(f"{what} = {int(radius_sq)} over a spacing of {int(w)} reaches {rho} voxels along {axis}, this version "
+                             f"supports a reach of at most {NEIGHBOUR_MAX_REACH} voxels on every axis; take a smaller radius")
+    return reach
+
+
+def neighbour_stats_settings(settings):
+    """count_blobs' cell neighbourhoods: None when settings["mi355x"]["neighbour_stats"] is absent, false or 0, else
+    (R2, (wz, wy, wx)): the key is the radius r, a number above 0 in the unit of depth_spacing - two cells are neighbours when a voxel
+    of one lies within r of a voxel of the other -, R2 = floor(r * r), and the spacing is settings["mi355x"]["depth_spacing"], three
+    integers 1..64 (default [1, 1, 1]).  ValueError, naming the key, for anything but such a number (a bool, a string, a negative
+    or non-finite value), for a radius below one spacing unit (R2 = 0: no two voxels are that close), for a bad spacing and for a
+    radius that reaches more than NEIGHBOUR_MAX_REACH voxels along an axis."""
+    mi = (settings or {}).get("mi355x") or {}
+    value = mi.get("neighbour_stats")
+    if not _neighbour_stats_given(mi):
+        return None
+    key = "settings['mi355x']['neighbour_stats']"
+    if not _is_number(value) or not math.isfinite(float(value)) or value < 0:
+        raise ValueError(f"{key} = {value!r}: expected the radius within which two cells are neighbours, a number above 0 in the unit "
+                         "of depth_spacing (0 / false: off)")
+    radius_sq = math.floor(float(value) * float(value)) if isinstance(value, (float, np.floating)) else int(value) * int(value)
+    if radius_sq < 1:
+        raise ValueError(f"{key} = {value!r}: a radius below one spacing unit finds no pair of voxels; expected at least 1")
+    spacing = _depth_spacing(mi)
+    spacing = (1, 1, 1) if spacing is None else spacing
+    neighbour_reach(radius_sq, spacing, f"{key} = {value!r}: the squared radius")
+    return radius_sq, spacing
+
+
+def neighbour_summary(pairs, gap_sq, n: int) -> dict:
+    """The per-cell rows of a neighbour table, host numpy work with no GPU.  pairs: (P, 2) labels a < b in 1..n, unique; gap_sq: (P)
+    their squared gaps, all >= 1.  -> N+1 rows each, row 0 zero: neighbour_count uint32, the degree of the cell in the graph;
+    nearest_gap_sq uint32, its smallest gap (0: no neighbour); nearest_cell uint32, the partner at that gap, the smallest label on a
+    tie (0: none); cluster_id uint32, the connected components of the graph numbered 1.. in the order of their smallest member (a
+    cell without a neighbour is a cluster of its own); cluster_size uint32, the cells of its cluster."""
+    n = int(n)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    gaps = np.asarray(gap_sq, dtype=np.int64).reshape(-1)
+    if len(gaps) != len(pairs):
+        raise ValueError(f"neighbour_summary: {len(pairs)} pairs beside {len(gaps)} gaps")
+    if len(pairs) and (pairs.min() < 1 or pairs.max() > n or (pairs[:, 0] >= pairs[:, 1]).any() or gaps.min() < 1):
+        raise ValueError(f"neighbour_summary: expected pairs a < b of labels 1..{n} with gaps >= 1")
+    src = np.concatenate([pairs[:, 0], pairs[:, 1]])
+    dst = np.concatenate([pairs[:, 1], pairs[:, 0]])
+    gap = np.concatenate([gaps, gaps])
+    count = np.bincount(src, minlength=n + 1).astype(np.uint32)
+    nearest_gap, nearest_cell = np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+    order = np.lexsort((dst, gap, src))  # by cell, then gap, then partner: the first row of a cell is its nearest
+    cells, first = np.unique(src[order], return_index=True)
+    nearest_gap[cells] = gap[order][first]
+    nearest_cell[cells] = dst[order][first]
+    cluster_id = np.zeros(n + 1, dtype=np.uint32)
+    if n > 0:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+
+        graph = coo_matrix((np.ones(len(pairs), dtype=np.int8), (pairs[:, 0] - 1, pairs[:, 1] - 1)), shape=(n, n))
+        _, comp = connected_components(graph, directed=False)
+        # (numbered in the order of their smallest member: of the first cell that belongs to them)
+        _, first_cell, inverse = np.unique(comp, return_index=True, return_inverse=True)
+        rank = np.empty(len(first_cell), dtype=np.int64)
+        rank[np.argsort(first_cell, kind="stable")] = np.arange(1, len(first_cell) + 1)
+        cluster_id[1:] = rank[inverse.reshape(-1)]
+    sizes = np.bincount(cluster_id, minlength=1)
+    sizes[0] = 0
+    return {"neighbour_count": count, "nearest_gap_sq": nearest_gap, "nearest_cell": nearest_cell, "cluster_id": cluster_id,
+            "cluster_size": sizes[cluster_id].astype(np.uint32)}
+
+
+def finish_neighbours(table: dict, n: int, radius_sq: int, spacing) -> dict:
+    """HipEngine.cc_neighbours' table of the labels 1..n, taken with `radius_sq` and `spacing` -> what count_blobs stores
+    (NEIGHBOUR_KEYS): neighbour_pairs uint32 (P, 2), a < b, sorted by (a, b); neighbour_gap_sq uint32 (P); neighbour_radius_sq and
+    neighbour_spacing, how they were measured; and neighbour_summary's per-cell rows."""
+    pairs = np.stack([np.asarray(table["a"], dtype=np.uint32), np.asarray(table["b"], dtype=np.uint32)], axis=1)
+    gaps = np.ascontiguousarray(table["gap_sq"], dtype=np.uint32)
+    out = {"neighbour_pairs": pairs, "neighbour_gap_sq": gaps, "neighbour_radius_sq": int(radius_sq),
+           "neighbour_spacing": tuple(int(w) for w in spacing)}
+    out.update(neighbour_summary(pairs, gaps, n))
+    return out
+
+
+def cell_neighbours_csv_text(stats: dict, n: int) -> str:
+    """count_blobs' cell_neighbours/<brain>.csv: header ``Blob,Size,Neighbours,NearestCell,NearestGapSq,NearestGap,Cluster,ClusterSize``,
+    one row per label 1..N - all N, as cell_depth_csv_text - integers written plainly, NearestGap = sqrt(NearestGapSq) as repr of the
+    float64 value (as depth_radius; 0.0 for a cell without a neighbour), every line ended by a newline."""
+    n = int(n)
+    ints = [np.asarray(stats[k])[1:n + 1].tolist() for k in ("voxel_counts", "neighbour_count", "nearest_cell", "nearest_gap_sq",
+                                                             "cluster_id", "cluster_size")]
+    gap = np.sqrt(np.asarray(stats["nearest_gap_sq"], dtype=np.float64))[1:n + 1].tolist()
+    if any(len(c) != n for c in ints + [gap]):
+        raise ValueError("statistics shorter than the label count")
+    lines = ["Blob,Size,Neighbours,NearestCell,NearestGapSq,NearestGap,Cluster,ClusterSize"]
+    lines.extend(f"{i},{c},{k},{nc},{g2},{g!r},{ci},{cs}" for i, (c, k, nc, g2, ci, cs, g) in enumerate(zip(*ints, gap), 1))
+    return "\n".join(lines) + "\n"
+
+
+def cell_pairs_csv_text(stats: dict) -> str:
+    """count_blobs' cell_pairs/<brain>.csv: header ``BlobA,BlobB,GapSq,Gap``, one row per pair of neighbour_pairs in its order (sorted
+    by (a, b)); Gap = sqrt(GapSq) as repr of the float64 value."""
+    pairs = np.asarray(stats["neighbour_pairs"]).reshape(-1, 2).tolist()
+    gaps = np.asarray(stats["neighbour_gap_sq"])
+    if len(gaps) != len(pairs):
+        raise ValueError("neighbour pairs and gaps of different lengths")
+    roots = np.sqrt(gaps.astype(np.float64)).tolist()
+    lines = ["BlobA,BlobB,GapSq,Gap"]
+    lines.extend(f"{a},{b},{g2},{g!r}" for (a, b), g2, g in zip(pairs, gaps.tolist(), roots))
     return "\n".join(lines) + "\n"
 
 
@@ -771,6 +902,7 @@ class CountOptions:
     label_file: str = "dense"  # label_file_format
     confidence: bool = False  # confidence_stats_enabled
     depth: Optional[Tuple[int, int, int]] = None  # depth_stats_settings
+    neighbours: Optional[Tuple[int, Tuple[int, int, int]]] = None  # neighbour_stats_settings: (R2, spacing)
     split_depth: Optional[Tuple[int, int, int, Tuple[int, int, int]]] = None  # split_depth_settings: (core_d2, fraction, min_core, spacing)
     fill_holes: bool = False  # fill_holes_enabled (the last field: tests/test_fill_holes_cpu.py pins it)
 
@@ -802,9 +934,10 @@ def count_options(settings, min_size, max_size) -> CountOptions:
     confidence = confidence_stats_enabled(settings)
     fill = fill_holes_enabled(settings)
     depth = depth_stats_settings(settings)
+    neighbours = neighbour_stats_settings(settings)
     return CountOptions(bounds=bounds, intensity=intensity_stats_enabled(settings), shell_radius=shell_radius, quartiles=quartiles,
                         shape=shape, split=split, label_file=label_file_format(settings), confidence=confidence,
-                        fill_holes=fill, depth=depth, split_depth=split_depth)
+                        fill_holes=fill, depth=depth, neighbours=neighbours, split_depth=split_depth)
 
 
 INTENSITY_STATS_KEYS = INTENSITY_KEYS + ("intensity_mean",)  # what settings["mi355x"]["intensity_stats"] adds to the statistics
@@ -823,16 +956,20 @@ def _same_setting(stored, asked) -> bool:
 def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     """The groups of per-cell statistics count_blobs has to measure: those `opts` asks for and `stats` - the cached pickle, None
     without one - does not hold completely.  A group is complete with every key of its row; a row that lists shell_radius also needs
-    the radius asked for (shells of another radius are other shells), and one that lists depth_spacing the spacing asked for."""
+    the radius asked for (shells of another radius are other shells), one that lists depth_spacing the spacing asked for, and the
+    neighbour table its own neighbour_radius_sq and neighbour_spacing (not depth_spacing: the two groups do not entangle)."""
     shell = opts.shell_radius > 0
-    settings_keys = {"shell_radius": opts.shell_radius, "depth_spacing": opts.depth}  # the keys that record how a row was measured
+    nb_radius_sq, nb_spacing = opts.neighbours if opts.neighbours is not None else (None, None)
+    settings_keys = {"shell_radius": opts.shell_radius, "depth_spacing": opts.depth,  # the keys that record how a row was measured
+                     "neighbour_radius_sq": nb_radius_sq, "neighbour_spacing": nb_spacing}
     rows = (("cells", opts.intensity, INTENSITY_STATS_KEYS),
             ("shell", opts.intensity and shell, SHELL_STATS_KEYS),
             ("cell_quartiles", opts.quartiles, QUARTILE_KEYS),
             ("shell_quartiles", opts.quartiles and shell, SHELL_QUARTILE_STATS_KEYS),
             ("shape", opts.shape, SHAPE_KEYS),
             ("confidence", opts.confidence, CONFIDENCE_KEYS),
-            ("depth", opts.depth is not None, DEPTH_KEYS))
+            ("depth", opts.depth is not None, DEPTH_KEYS),
+            ("neighbours", opts.neighbours is not None, NEIGHBOUR_KEYS))
 
     def complete(keys) -> bool:
         return (stats is not None and all(k in stats for k in keys)
@@ -841,8 +978,8 @@ def measuring_plan(opts: CountOptions, stats: Optional[dict]) -> frozenset:
     return frozenset(group for group, asked, keys in rows if asked and not complete(keys))
 
 
-_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "depth_stats", "split_fused", "split_radius", "size_filter", "label_file")
-_HBM_CACHED = ("label_file", "shape_stats", "depth_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
+_HBM_FRESH = ("fill_holes", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats", "shape_stats", "depth_stats", "neighbour_stats", "split_fused", "split_radius", "size_filter", "label_file")
+_HBM_CACHED = ("label_file", "shape_stats", "depth_stats", "neighbour_stats", "intensity_stats", "background_shell", "intensity_quartiles", "confidence_stats")  # (cached labels are not split or filtered)
 
 
 def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxels: int, budget: int, runs_decoded: bool = False) -> None:
@@ -867,6 +1004,8 @@ def check_hbm_budget(opts: CountOptions, measured, cached: bool, base: int, voxe
         "confidence_stats": ("confidence" in measured, "", 4, f"the probabilities (4 more bytes per voxel) in HBM beside {resident}", "measure"),
         "shape_stats": ("shape" in measured, "", 0, f"{resident} in HBM", "measure"),
         "depth_stats": ("depth" in measured, "", 8, f"8 more bytes per voxel in HBM beside {resident}", "measure"),
+        # (the pair table and the outputs of the neighbour table are sized from the count: HipEngine.cc_neighbours checks them)
+        "neighbour_stats": ("neighbours" in measured, "", 0, f"{resident} in HBM", "measure"),
         "split_fused": (opts.split is not None, f" = {opts.split and opts.split[0]}", 8,
                         f"8 more bytes per voxel in HBM beside {resident}", "split"),
         "split_radius": (opts.split_depth is not None, " / ['split_fraction']", 8,

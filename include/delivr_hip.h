@@ -480,6 +480,34 @@ int dlv_cc_overlap_count_dev(dlv_ctx* ctx, const uint32_t* a_dev, const uint32_t
 int dlv_cc_overlap_dev(dlv_ctx* ctx, const uint32_t* a_dev, const uint32_t* b_dev, int Z, int Y, int X, uint64_t n_a, uint64_t n_b,
                        uint64_t n_segments, uint64_t* table_dev, uint64_t cap, uint64_t* keys_out_dev, uint64_t* voxels_out_dev,
                        uint64_t out_cap, uint64_t* n_pairs);
+/* The neighbour table of a label volume (no counterpart in the reference; csrc/cc_neighbours.hip, count_blobs' neighbour_stats): every
+ * pair of labels a < b whose cells come within a radius of each other, with the exact smallest squared distance between them.
+ * labels_dev: uint32 (Z,Y,X) contiguous, 4-byte aligned, not written. A voxel takes part when 1 <= L(v) <= n: the background and
+ * labels above n contribute nothing and block nothing. wz, wy, wx: the voxel spacings, integers 1..64 (as dlv_cc_depth_dev);
+ * r2 >= 1: the squared radius in spacing units. gap2(a, b) = the minimum over the voxels v of a and u of b of
+ * (wz (vz - uz))^2 + (wy (vy - uy))^2 + (wx (vx - ux))^2, at least 1; the table is every a < b with gap2(a, b) <= r2, under the key
+ * (a << 32) | b. The reach along axis a is floor(sqrt(r2) / w_a) voxels; this version supports a reach of at most 8 on every axis
+ * (0 is legal: no offsets along that axis). A segment is one flush of a thread's carry (one pair, its smallest distance so far)
+ * in the scan of the surface voxels; both entries make the same scan.
+ *  dlv_cc_neighbours_count_dev: *n_segments = the segments S of the volume, on the host. The pairs P are at most
+ *    min(S, n (n - 1) / 2). Synchronous.
+ *  dlv_cc_neighbours_dev: with the S of the count on the same volume and arguments, the P keys go to keys_out_dev[0..P) (uint64,
+ *    8-byte aligned) and their gap2 to gap2_out_dev[0..P) (uint32, 4-byte aligned), out_cap >= min(S, n (n - 1) / 2) entries each,
+ *    *n_pairs = P on the host. table_dev: the caller's scratch of cap slots of 16 bytes (2 * cap uint64, 16-byte aligned), cap a
+ *    power of two >= 2 * min(S, n (n - 1) / 2); the call clears it. The order of the pairs on the device is unspecified
+ *    (HipEngine.cc_neighbours sorts by key on the host); the pairs and their gaps are exact and independent of scheduling: integer
+ *    work only. With S = 0 nothing is launched and P = 0. Synchronous.
+ * DLV_EINVAL, checked on the host before anything is launched and with nothing written: a NULL pointer, a misaligned pointer,
+ * Z/Y/X < 1, a spacing outside 1..64, r2 < 1, n above 2^32 - 2, cap not a power of two or below 2 * min(S, n (n - 1) / 2), out_cap
+ * below min(S, n (n - 1) / 2), a volume beyond the launch grid (more than 65535 tiles of 8 planes or of 8 rows). DLV_EUNSUP, checked
+ * in the same place, with a message that names the axis, its reach and the limit: a reach above 8; and X above 2^30. DLV_ESTATE with a
+ * message that names the table: a key found no slot, or more pairs than out_cap - the kernels bound every probe by cap and every
+ * write by out_cap, and neither happens when S is the count of this volume. */
+int dlv_cc_neighbours_count_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx,
+                                uint64_t r2, uint64_t* n_segments);
+int dlv_cc_neighbours_dev(dlv_ctx* ctx, const uint32_t* labels_dev, int Z, int Y, int X, uint64_t n, int wz, int wy, int wx, uint64_t r2,
+                          uint64_t n_segments, uint64_t* table_dev, uint64_t cap, uint64_t* keys_out_dev, uint32_t* gap2_out_dev,
+                          uint64_t out_cap, uint64_t* n_pairs);
 
 /* ---- TIFF z-plane ingest -------------------------------------------------------- */
 /* Replaces the per-plane cv2.imread / skimage.io / tifffile reads of the raw stack
